@@ -6,6 +6,14 @@ host finalize — i.e. the whole reference pipeline of SURVEY.md §3.4 with
 scan IO excluded (inputs resident, `data: synthetic`).
 
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--sf S]
+                        [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: generate the
+resident columns, warm up, time the K steps, print the result line.
+--full adds every other leg to the same line: the CPU-oracle baseline and
+(for the default q1) the folded q6 / q3 / end-to-end Parquet blocks.
+--dump-outputs DIR writes what the last timed step returned to its caller
+as DIR/<name>.npy (float64; string columns as dictionary codes).
 Multi-rank: launched by torch.distributed.run, one rank per GPU (weak
 scaling: each rank owns a full SF-sized shard; the only exchange on Q1's
 path is the 384-byte partial-aggregate combine — SURVEY.md §8e / BASELINE
@@ -14,8 +22,9 @@ configs[1] is "no shuffle" — done host-side via gloo).
 Prints ONE JSON line from rank 0 (driver contract), including:
   roofline      — dominant-kernel HBM roofline measured with HIP events on
                   the launching stream (38 algorithmic B/row)
-  cpu_baseline  — the CPU oracle (numpy restatement, oracle/queries.py)
-                  timed on this box's host cores over a bounded sample
+  cpu_baseline  — (--full only, else null) the CPU oracle (numpy
+                  restatement, oracle/queries.py) timed on this box's host
+                  cores over a bounded sample
 """
 import argparse
 import json
@@ -57,13 +66,45 @@ def parse_args():
                    help="A/B: sequential exchange -> probe (round-1 path)")
     p.add_argument("--nt", type=int, default=1,
                    help="non-temporal probe loads (Q3/Q5)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs the headline figure does not "
+                        "need: the CPU-oracle baseline and, for q1, the "
+                        "folded q6/q3/e2e blocks")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's "
+                        "result arrays to DIR/<name>.npy")
     p.add_argument("--cpu-sample-rows", type=int, default=12_000_000)
-    p.add_argument("--skip-cpu-baseline", action="store_true")
+    p.add_argument("--skip-cpu-baseline", action="store_true",
+                   help="--full: leave out the CPU-oracle baseline")
     p.add_argument("--skip-subbench", action="store_true",
-                   help="q1 default run: skip the folded q3/q6/e2e legs")
+                   help="--full q1 run: skip the folded q3/q6/e2e legs")
     p.add_argument("--e2e-sf", type=float, default=10.0,
                    help="scale factor of the end-to-end Parquet leg")
     return p.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64 << 20         # --dump-outputs writes at most this much
+
+
+def dump_outputs(outdir, arrays):
+    """Write a result table (name -> array) as outdir/<name>.npy, float64.
+    String columns become their dictionary codes (index into the sorted
+    distinct values). A table over the byte budget is cut to a fixed
+    seeded sample of rows, the same rows for every column of equal
+    length and for every run."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    per = max(1, DUMP_BUDGET_BYTES // 8 // max(1, len(arrays)))
+    for name, a in arrays.items():
+        a = a.reshape(-1)
+        if a.size > per:
+            idx = np.random.default_rng(0).choice(a.size, per, replace=False)
+            idx.sort()
+            a = a[idx]
+        if a.dtype.kind in "USO":
+            a = np.unique(a, return_inverse=True)[1]
+        np.save(os.path.join(outdir, name + ".npy"),
+                np.ascontiguousarray(a, dtype=np.float64))
 
 
 def gen_device_lineitem(shim, n, rank):
@@ -557,10 +598,13 @@ def main_q3(args, n, world, rank, dist, shim, DQ, standalone=True):
                            "exchange+probe sequential" if use_exchange
                            else "probe kernel"),
             },
-            "cpu_baseline": (None if args.skip_cpu_baseline or world > 1
-                             else cpu_baseline_q3(args.cpu_sample_rows)),
+            "cpu_baseline": (cpu_baseline_q3(args.cpu_sample_rows)
+                             if args.full and not args.skip_cpu_baseline
+                             and world == 1 else None),
         }
         if standalone:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, top10)
             print(json.dumps(out))
     else:
         out = None
@@ -675,10 +719,15 @@ def main_q5(args, n, world, rank, dist, shim, DQ, standalone=True):
                 "frac": achieved_gbps / HBM_PEAK_GBPS,
                 "traffic": read_traffic(args.sf, "q5"),
             },
-            "cpu_baseline": (None if args.skip_cpu_baseline or world > 1
-                             else cpu_baseline_q5(args.cpu_sample_rows)),
+            "cpu_baseline": (cpu_baseline_q5(args.cpu_sample_rows)
+                             if args.full and not args.skip_cpu_baseline
+                             and world == 1 else None),
         }
         if standalone:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs,
+                             {"nation": [nm for nm, _ in res],
+                              "revenue": [r for _, r in res]})
             print(json.dumps(out))
     else:
         out = None
@@ -766,6 +815,9 @@ def main_q6(args, n, world, rank, dist, shim, DQ, cols=None,
             "cpu_baseline": None,
         }
         if standalone:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, {"revenue": res[:, 0],
+                                                 "rows_passed": res[:, 1]})
             print(json.dumps(out))
     else:
         out = None
@@ -822,6 +874,10 @@ def main_q4(args, n, world, rank, dist, shim, DQ, standalone=True):
                        "query": "Q4", "result": res},
         }
         if standalone:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs,
+                             {"o_orderpriority": list(res.keys()),
+                              "order_count": list(res.values())})
             print(json.dumps(out))
     for c in list(li.values()) + list(od.values()):
         c.free()
@@ -873,6 +929,8 @@ def main_q18(args, n, world, rank, dist, shim, DQ, standalone=True):
                        "qualifying_orders": len(res["o_orderkey"])},
         }
         if standalone:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, res)
             print(json.dumps(out))
     for c in list(li.values()) + list(od.values()):
         c.free()
@@ -986,9 +1044,10 @@ def main():
     # resident Q1 columns; Q3 (and the RCCL exchange at world>1) and the
     # end-to-end Parquet leg run after the Q1 columns are freed.
     subs = {}
-    if args.query == "q1" and not args.skip_subbench:
+    if args.query == "q1" and args.full and not args.skip_subbench:
         import argparse as _ap
         sub = _ap.Namespace(**vars(args))
+        sub.dump_outputs = None
         sub.steps = max(3, min(10, args.steps))
         sub.warmup = max(1, min(3, args.warmup))
         sub.cpu_sample_rows = min(args.cpu_sample_rows, 6_000_000)
@@ -1041,14 +1100,17 @@ def main():
                 "frac": achieved_gbps / HBM_PEAK_GBPS,
                 "traffic": traffic,
             },
-            "cpu_baseline": (None if args.skip_cpu_baseline or world > 1
-                             else cpu_baseline(args.cpu_sample_rows)),
+            "cpu_baseline": (cpu_baseline(args.cpu_sample_rows)
+                             if args.full and not args.skip_cpu_baseline
+                             and world == 1 else None),
             "q1_result_rows": len(result["count_order"]) if result else 0,
         }
         # folded legs: Q6 (JIT scan), Q3 (join+group-by, the north_star
         # core; RCCL-exchanged and overlapped at world>1), e2e Parquet —
         # each with its own HIP-event roofline, same record
         out.update(subs)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, result)
         print(json.dumps(out))
 
     timer.destroy()
