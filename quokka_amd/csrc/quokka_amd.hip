@@ -2695,7 +2695,7 @@ __global__ void k_snappy_pages(uint64_t npages,
     ip = p;
   }
   if (ulen != expect) {
-    if (lane == 0) { o[0] = 0; o[1] = 2; o[2] = 0; }
+    if (lane == 0) { o[0] = 0; o[1] = 2; o[2] = 0; o[3] = 0; }
     return;
   }
 
@@ -2711,6 +2711,7 @@ __global__ void k_snappy_pages(uint64_t npages,
       len = (tag >> 2) + 1;
       if (len > 60) {
         int nb = (int)len - 60;
+        if (iend - ip < nb) { err = 1; break; }   // length bytes cut off
         len = 0;
         for (int k = 0; k < nb; k++) len |= (uint64_t)ip[k] << (8 * k);
         len += 1;
@@ -2720,6 +2721,10 @@ __global__ void k_snappy_pages(uint64_t npages,
       for (uint64_t k = lane; k < len; k += 64) op0[opos + k] = ip[k];
       ip += len;
     } else {
+      // the 1/2/4 offset bytes must lie inside this page's slice: a
+      // stream cut short must not borrow them from the next page
+      int nb = (tag & 3) == 1 ? 1 : (tag & 3) == 2 ? 2 : 4;
+      if (iend - ip < nb) { err = 1; break; }
       if ((tag & 3) == 1) {                       // copy1: 4..11 bytes
         len = 4 + ((tag >> 2) & 7);
         cof = ((uint64_t)(tag >> 5) << 8) | *ip;
@@ -2850,7 +2855,11 @@ struct BitReader {
     bitcnt -= n;
     return v;
   }
+  // Drop the rest of the current byte. peek() may have fetched whole
+  // bytes that were never consumed (up to 17 bits for a 10-bit lookup):
+  // hand them back to p before the buffer is cleared.
   __device__ void align_byte() {
+    p -= bitcnt >> 3;
     bitbuf = 0; bitcnt = 0;
   }
   __device__ uint32_t peek(int n) {      // pads zeros past the end
@@ -3012,9 +3021,9 @@ __global__ void __launch_bounds__(64) k_gzip_pages(
     if (br.fail) { o[1] = 1; return; }
     if (btype == 0) {                    // stored
       br.align_byte();
-      // br.p already consumed whole bytes; realign: p points past
-      // consumed bytes (bitbuf dropped) — p is correct since bits()
-      // only advances p per byte
+      // LEN/NLEN start at the next byte boundary. decode_fast's peek()
+      // of the previous block can leave a whole unconsumed byte in
+      // bitbuf, so align_byte() re-synchronises p before dropping it
       if (br.end - br.p < 4) { o[1] = 1; return; }
       uint32_t len = br.p[0] | ((uint32_t)br.p[1] << 8);
       uint32_t nlen = br.p[2] | ((uint32_t)br.p[3] << 8);

@@ -58,16 +58,20 @@ def _tile_block(data_off, dst_row, num_values, elem_size):
     return out
 
 
-def _check_levels_v1(buf, pos, num_values, max_def):
+def _check_levels_v1(buf, pos, num_values, max_def, page_end=None):
     """Definition-levels block of a v1 data page ([u32 len][RLE runs]).
     Verify every level == max_def (no nulls) without expanding; return
-    the position after the block."""
+    the position after the block. With page_end (the position after the
+    page's last byte) a block that claims to run past its page is
+    refused, as k_snappy_pages refuses it (err 1)."""
     if max_def.bit_length() != 1:
         raise QkParquetError("nested schemas unsupported (max_def=%d)"
                              % max_def)
     ln = int.from_bytes(buf[pos:pos + 4], "little")
     p = pos + 4
     end = p + ln
+    if page_end is not None and (p > page_end or end > page_end):
+        raise QkParquetError("definition levels run past the page")
     seen = 0
     while seen < num_values and p < end:
         h, p = _varint(buf, p)
@@ -159,7 +163,8 @@ class _Chunk:
                 data = p.data_off
                 if max_def > 0:
                     data = _check_levels_v1(buf, data, p.num_values,
-                                            max_def)
+                                            max_def,
+                                            p.data_off + p.data_len)
             else:                       # v2: levels first, lengths known
                 if p.num_nulls:
                     raise QkParquetError("page contains nulls")
@@ -446,7 +451,8 @@ def _snappy_column(shim, raw, dev_file, cols_meta, max_def, dst0):
             if p.kind == T.PAGE_DATA:
                 if max_def > 0:
                     data_abs = _check_levels_v1(raw, data_abs,
-                                                p.num_values, max_def)
+                                                p.num_values, max_def,
+                                                p.data_off + p.data_len)
             else:
                 if p.num_nulls:
                     raise QkParquetError("page contains nulls")

@@ -339,6 +339,87 @@ def test_gzip_nullable_v1_raises(gpu):
         P.read_table(raw)
 
 
+def _flushed_gzip_chunk():
+    """A column chunk of two v1 PLAIN INT64 data pages, written by hand:
+    each page is a Thrift compact PageHeader plus a gzip stream that a
+    flushing writer could produce. Page 0 is a Huffman block followed by
+    the empty stored block of a full flush; page 1 sync-flushes midway.
+    Returns (raw bytes, chunk metadata, int64 values)."""
+    import gzip
+    import struct
+    import types
+    import zlib
+
+    def zz(n):                              # zigzag varint
+        n <<= 1
+        out = bytearray()
+        while n >= 0x80:
+            out.append((n & 0x7F) | 0x80)
+            n >>= 7
+        out.append(n)
+        return bytes(out)
+
+    def page(payload, body):
+        # PageHeader{1: type=DATA_PAGE, 2: uncompressed, 3: compressed,
+        #   5: DataPageHeader{1: num_values, 2: PLAIN, 3: RLE, 4: RLE}}
+        hdr = (b"\x15" + zz(0) + b"\x15" + zz(len(payload))
+               + b"\x15" + zz(len(body)) + b"\x2c"
+               + b"\x15" + zz(len(payload) // 8) + b"\x15" + zz(0)
+               + b"\x15" + zz(3) + b"\x15" + zz(3) + b"\x00\x00")
+        return hdr + body
+
+    def gz(payload, strategy, flush, at):
+        c = zlib.compressobj(6, zlib.DEFLATED, -15, 9, strategy)
+        raw = (c.compress(payload[:at]) + c.flush(flush)
+               + c.compress(payload[at:]) + c.flush())
+        body = (b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\x03" + raw
+                + struct.pack("<II", zlib.crc32(payload), len(payload)))
+        assert gzip.decompress(body) == payload
+        return body
+
+    p0 = b"the quick brown fox 64 " * 64        # 1472 bytes = 184 int64
+    p1 = np.arange(1000, 1300, dtype=np.int64).tobytes()
+    pages = (page(p0, gz(p0, zlib.Z_RLE, zlib.Z_FULL_FLUSH, len(p0) - 1))
+             + page(p1, gz(p1, zlib.Z_DEFAULT_STRATEGY, zlib.Z_SYNC_FLUSH,
+                           len(p1) // 2)))
+    lead = b"PAR1" + b"\x00" * 3
+    raw = lead + pages + b"\x00" * 16
+    values = np.frombuffer(p0 + p1, dtype=np.int64)
+    col = types.SimpleNamespace(
+        compression="GZIP", physical_type="INT64",
+        data_page_offset=len(lead), dictionary_page_offset=None,
+        total_compressed_size=len(pages), num_values=len(values))
+    return raw, col, values
+
+
+def test_gzip_chunk_with_flushed_streams(gpu):
+    """The gzip branch of the chunk-decompress routine on pages from a
+    writer that flushes: a stored block right after a Huffman block used
+    to be refused as 'corrupt stream'."""
+    from quokka_amd import parquet_gpu as P
+    from quokka_amd import parquet_thrift as T
+    raw, col, values = _flushed_gzip_chunk()
+    pl = T.walk_pages(raw, col.data_page_offset,
+                      col.total_compressed_size, col.num_values)
+    assert [(p.kind, p.num_values, p.encoding) for p in pl] \
+        == [(T.PAGE_DATA, 184, P.ENC_PLAIN), (T.PAGE_DATA, 300,
+                                             P.ENC_PLAIN)]
+    dev_file = P._upload(gpu, raw)
+    scratch = None
+    try:
+        chunks, scratch = P._snappy_column(gpu, raw, dev_file, [col], 0, 0)
+        out = P._decode_column(gpu, scratch, chunks, len(values))
+        gpu.call("qk_stream_sync", None)
+        try:
+            np.testing.assert_array_equal(out.to_numpy(out.n), values)
+        finally:
+            out.free()
+    finally:
+        dev_file.free()
+        if scratch is not None:
+            scratch.free()
+
+
 def test_gzip_lineitem_q6(gpu):
     """GZIP lineitem -> GPU inflate + decode -> Q6 == oracle."""
     from oracle import tpch_gen as G, queries as OQ
