@@ -488,6 +488,80 @@ int qk_str_dict_rehash(void *stream, uint32_t ncodes,
                        const uint64_t *code_off, const uint32_t *code_len,
                        const uint8_t *arena, uint64_t *slot_hash,
                        int32_t *slot_code, uint64_t capacity);
+/* ---- LIKE over free-text string columns ------------------------------- *
+ * The reference hands `col LIKE 'pat'` / NOT LIKE / = / <> on varchar
+ * columns to DuckDB or polars inside filter_sql (core.py:157-163; the
+ * TPC-H call sites are apps/tpc-h/tpch.py:137,316,380,389,413,416,481).
+ * Semantics: DuckDB's default LIKE — case-sensitive, % = any run of bytes
+ * (empty included), _ = exactly one UTF-8 code point, no ESCAPE clause
+ * (backslash is an ordinary byte).
+ *
+ * qk_like_pat is the compiled pattern: the pattern bytes with every '%'
+ * removed, cut into at most QK_LIKE_MAX_SEGS non-empty segments (runs of
+ * literal bytes and _ wildcards between % signs), plus whether the first
+ * segment is anchored at the start and the last at the end. `wild` marks
+ * which bytes of `pat` are _ wildcards; exact patterns (= / <>) have none
+ * and a single doubly-anchored segment. Plain data, passed to the kernel
+ * by value. */
+#define QK_LIKE_MAX_PAT 256
+#define QK_LIKE_MAX_SEGS 16
+typedef struct {
+  uint32_t nseg;
+  uint8_t anchor_start;
+  uint8_t anchor_end;
+  uint8_t exact;
+  uint8_t pad_;
+  uint16_t seg_off[QK_LIKE_MAX_SEGS]; /* into pat */
+  uint16_t seg_len[QK_LIKE_MAX_SEGS];
+  uint32_t wild[QK_LIKE_MAX_PAT / 32]; /* bit k: pat[k] is a _ wildcard */
+  uint8_t pat[QK_LIKE_MAX_PAT];
+} qk_like_pat;
+/* Host only: compile SQL pattern bytes (exact != 0: every byte literal,
+ * the = / <> form; replaces the pattern handling DuckDB does for
+ * tpch.py:380 `o_comment not like '%special%requests%'` and :416
+ * `p_brand != 'Brand#45'`). Returns non-zero, with qk_last_error set, for
+ * len > QK_LIKE_MAX_PAT or more than QK_LIKE_MAX_SEGS segments — never
+ * truncates. */
+int qk_like_compile(const uint8_t *pat, uint32_t len, int exact,
+                    qk_like_pat *out);
+/* Per-row match over an Arrow string column (offsets[n+1] + bytes, both
+ * device pointers): out_flags[r] = match(row r) ^ (negate != 0), 0 or 1
+ * (tpch.py:380 filter_sql("o_comment not like ..."), :413, :316, :481).
+ * One block handles 256 consecutive rows, whose bytes are one contiguous
+ * span. For a pattern with a searched segment (a % before or between
+ * literals), spans that fit the LDS tile (qk_like_tile_bytes) are staged
+ * into LDS with 16-byte loads and matched from there; longer spans, and
+ * every span of a pattern made of anchored segments only (prefix, suffix,
+ * equality: a few bytes per row), are matched straight from global memory
+ * by the same matcher. i32 = Arrow `string`
+ * offsets, i64 = `large_string`. `pat` is a HOST pointer. n == 0 returns
+ * 0 without a launch. */
+int qk_str_like_i32(void *stream, uint64_t n, const int32_t *offsets,
+                    const uint8_t *bytes, const qk_like_pat *pat, int negate,
+                    uint8_t *out_flags);
+int qk_str_like_i64(void *stream, uint64_t n, const int64_t *offsets,
+                    const uint8_t *bytes, const qk_like_pat *pat, int negate,
+                    uint8_t *out_flags);
+/* The two above with the path chosen by the caller (stage != 0: LDS
+ * staging for spans that fit; 0: every block direct from global memory)
+ * instead of by the pattern's shape: the A/B of scripts/bench_like.py and
+ * the tests of either path. Same results. */
+int qk_str_like_path_i32(void *stream, uint64_t n, const int32_t *offsets,
+                         const uint8_t *bytes, const qk_like_pat *pat,
+                         int negate, int stage, uint8_t *out_flags);
+int qk_str_like_path_i64(void *stream, uint64_t n, const int64_t *offsets,
+                         const uint8_t *bytes, const qk_like_pat *pat,
+                         int negate, int stage, uint8_t *out_flags);
+/* The same matcher in a plain CPU loop over HOST pointers (what DuckDB's
+ * LIKE computes for tpch.py:380 on the host): the CPU tests reach the
+ * shared __host__ __device__ matcher through this. */
+int qk_str_like_host_i64(uint64_t n, const int64_t *offsets,
+                         const uint8_t *bytes, const qk_like_pat *pat,
+                         int negate, uint8_t *out_flags);
+/* Bytes of the LDS tile of qk_str_like_* (a block's span, plus up to 15
+ * bytes of alignment shift, must fit it to take the staged path). Returns
+ * the size, not an error code. */
+int qk_like_tile_bytes(void);
 /* Composite i64 key column: out = x * scale + y (per-(a,b) group keys,
  * e.g. Q20's (partkey, suppkey) quantity sums). */
 int qk_i64_combine(void *stream, uint64_t n, const int64_t *x,

@@ -2598,6 +2598,285 @@ extern "C" int qk_str_dict_rehash(void *stream, uint32_t ncodes,
   return 0;
 }
 
+// ---- LIKE over free-text string columns --------------------------------
+// filter_sql("o_comment not like '%special%requests%'") and its kin
+// (apps/tpc-h/tpch.py:137,316,380,413,416,481) run inside DuckDB/polars in
+// the reference. Here: one thread per row runs qk_like_match over the
+// row's bytes. A block's 256 rows are one contiguous byte span, so the
+// block first copies the span into LDS with coalesced 16-byte loads and
+// the lanes then walk their rows out of LDS; a span that does not fit the
+// tile (long strings) is matched straight from global memory by the same
+// function, and so is every span of a pattern that only looks at a row's
+// ends (qk_like_wants_stage). No atomics, no scratch buffers.
+static_assert(sizeof(qk_like_pat) == 360, "qk_like_pat layout (shim.LikePat)");
+#define QK_LIKE_TILE 24576  // + 360 B pattern: 6 blocks/CU within 160 KiB
+
+extern "C" int qk_like_compile(const uint8_t *pat, uint32_t len, int exact,
+                               qk_like_pat *out) {
+  memset(out, 0, sizeof(*out));
+  if (len > QK_LIKE_MAX_PAT) {
+    snprintf(g_err, sizeof(g_err),
+             "qk_like_compile: pattern of %u bytes exceeds %d", len,
+             QK_LIKE_MAX_PAT);
+    g_err_set = 1;
+    return (int)hipErrorInvalidValue;
+  }
+  out->exact = exact ? 1 : 0;
+  if (exact) {
+    out->anchor_start = out->anchor_end = 1;
+    if (len) {
+      out->nseg = 1;
+      out->seg_len[0] = (uint16_t)len;
+      memcpy(out->pat, pat, len);
+    }
+    return 0;
+  }
+  out->anchor_start = !(len && pat[0] == '%');
+  out->anchor_end = !(len && pat[len - 1] == '%');
+  uint32_t w = 0;       // bytes written to out->pat
+  int open = 0;         // inside a segment
+  for (uint32_t i = 0; i < len; i++) {
+    if (pat[i] == '%') {
+      open = 0;
+      continue;
+    }
+    if (!open) {
+      if (out->nseg == QK_LIKE_MAX_SEGS) {
+        snprintf(g_err, sizeof(g_err),
+                 "qk_like_compile: more than %d segments", QK_LIKE_MAX_SEGS);
+        g_err_set = 1;
+        return (int)hipErrorInvalidValue;
+      }
+      out->seg_off[out->nseg++] = (uint16_t)w;
+      open = 1;
+    }
+    if (pat[i] == '_') out->wild[w >> 5] |= 1u << (w & 31);
+    out->pat[w++] = pat[i];
+    out->seg_len[out->nseg - 1]++;
+  }
+  return 0;
+}
+
+// UTF-8 continuation byte (10xxxxxx): never the start of a code point.
+static __host__ __device__ inline bool qk_u8_cont(uint8_t b) {
+  return (b & 0xC0) == 0x80;
+}
+static __host__ __device__ inline bool qk_like_wild(const qk_like_pat *p,
+                                                    uint32_t k) {
+  return (p->wild[k >> 5] >> (k & 31)) & 1u;
+}
+// Segment `g` matched forward at s[pos..limit): end position, or -1.
+static __host__ __device__ inline int64_t qk_like_fwd(
+    const qk_like_pat *p, uint32_t g, const uint8_t *s, uint32_t pos,
+    uint32_t limit) {
+  uint32_t k = p->seg_off[g], ke = k + p->seg_len[g];
+  for (; k < ke; k++) {
+    if (pos >= limit) return -1;
+    if (qk_like_wild(p, k)) {
+      pos++;
+      while (pos < limit && qk_u8_cont(s[pos])) pos++;
+    } else {
+      if (s[pos] != p->pat[k]) return -1;
+      pos++;
+    }
+  }
+  return (int64_t)pos;
+}
+// Segment `g` matched backward so that it ends at `end` and starts no
+// earlier than `lower`: start position, or -1.
+static __host__ __device__ inline int64_t qk_like_bwd(
+    const qk_like_pat *p, uint32_t g, const uint8_t *s, uint32_t end,
+    uint32_t lower) {
+  uint32_t k0 = p->seg_off[g], k = k0 + p->seg_len[g];
+  uint32_t q = end;
+  while (k > k0) {
+    k--;
+    if (q <= lower) return -1;
+    if (qk_like_wild(p, k)) {
+      q--;
+      while (q > lower && qk_u8_cont(s[q])) q--;
+      if (qk_u8_cont(s[q])) return -1;  // code point starts below `lower`
+    } else {
+      q--;
+      if (s[q] != p->pat[k]) return -1;
+    }
+  }
+  return (int64_t)q;
+}
+// The per-row matcher, shared by the kernel and qk_str_like_host_i64.
+// Anchored first segment at 0, anchored last segment at the end (not
+// overlapping what came before), the rest by leftmost search in order —
+// exact for a wildcard set of % and _.
+static __host__ __device__ inline bool qk_like_match(const qk_like_pat *p,
+                                                     const uint8_t *s,
+                                                     uint32_t len) {
+  uint32_t nseg = p->nseg;
+  if (!nseg) return (p->anchor_start && p->anchor_end) ? len == 0 : true;
+  uint32_t pos = 0, first = 0, last = nseg, limit = len;
+  if (p->anchor_start) {
+    int64_t e = qk_like_fwd(p, 0, s, 0, len);
+    if (e < 0) return false;
+    pos = (uint32_t)e;
+    first = 1;
+    if (nseg == 1 && p->anchor_end) return pos == len;  // no % at all
+  }
+  if (p->anchor_end && last > first) {
+    int64_t b = qk_like_bwd(p, nseg - 1, s, len, pos);
+    if (b < 0) return false;
+    limit = (uint32_t)b;
+    last = nseg - 1;
+  }
+  for (uint32_t g = first; g < last; g++) {
+    uint32_t k0 = p->seg_off[g];
+    bool lit0 = !qk_like_wild(p, k0);
+    uint8_t c0 = p->pat[k0];
+    int64_t e = -1;
+    for (; pos < limit; pos++) {
+      uint8_t b = s[pos];
+      if (lit0 ? b != c0 : qk_u8_cont(b)) continue;
+      e = qk_like_fwd(p, g, s, pos, limit);
+      if (e >= 0) break;
+    }
+    if (e < 0) return false;
+    pos = (uint32_t)e;
+  }
+  return true;
+}
+
+template <typename OffT, bool STAGE>
+__global__ void __launch_bounds__(BLOCK) k_str_like(
+    uint64_t n, const OffT *__restrict__ offsets,
+    const uint8_t *__restrict__ bytes, const qk_like_pat pat, int negate,
+    uint8_t *__restrict__ out) {
+  __shared__ qk_like_pat sp;
+  __shared__ __attribute__((aligned(16))) uint8_t tile[STAGE ? QK_LIKE_TILE : 16];
+  {
+    const uint32_t *src = (const uint32_t *)&pat;
+    uint32_t *dst = (uint32_t *)&sp;
+    for (uint32_t i = threadIdx.x; i < sizeof(qk_like_pat) / 4; i += BLOCK)
+      dst[i] = src[i];
+  }
+  __syncthreads();
+  uint8_t neg = negate ? 1 : 0;
+  for (uint64_t r0 = (uint64_t)blockIdx.x * BLOCK; r0 < n;
+       r0 += (uint64_t)gridDim.x * BLOCK) {
+    uint64_t r1 = qk_min_u64(n, r0 + BLOCK);
+    uint64_t lo = (uint64_t)offsets[r0], hi = (uint64_t)offsets[r1];
+    uint64_t span = hi >= lo ? hi - lo : ~0ULL;
+    const uint8_t *g = bytes + lo;
+    // tile[shift + i] holds byte lo + i, so 16-byte-aligned global chunks
+    // land 16-byte-aligned in LDS
+    uint32_t shift = (uint32_t)((uintptr_t)g & 15);
+    bool staged = STAGE && span + shift <= QK_LIKE_TILE;
+    if (staged) {
+      uint32_t sp32 = (uint32_t)span;
+      uint32_t head = (16 - shift) & 15;           // bytes before alignment
+      if (head > sp32) head = sp32;
+      uint32_t nvec = (sp32 - head) / 16;          // whole aligned chunks
+      uint32_t tail0 = head + nvec * 16;
+      if (threadIdx.x < head) tile[shift + threadIdx.x] = g[threadIdx.x];
+      const uint4 *gv = (const uint4 *)(g + head);
+      uint4 *tv = (uint4 *)(tile + shift + head);
+      for (uint32_t i = threadIdx.x; i < nvec; i += BLOCK) tv[i] = gv[i];
+      if (threadIdx.x < sp32 - tail0)
+        tile[shift + tail0 + threadIdx.x] = g[tail0 + threadIdx.x];
+      __syncthreads();
+    }
+    uint64_t r = r0 + threadIdx.x;
+    if (r < r1) {
+      uint64_t o0 = (uint64_t)offsets[r], o1 = (uint64_t)offsets[r + 1];
+      bool m;
+      if (staged) {
+        // clamp into the staged span: LDS reads stay inside the tile even
+        // for offsets that are not monotone
+        uint64_t a = o0 >= lo ? o0 - lo : 0, b = o1 >= lo ? o1 - lo : 0;
+        a = qk_min_u64(a, span);
+        b = qk_min_u64(b < a ? a : b, span);
+        m = qk_like_match(&sp, tile + shift + (uint32_t)a, (uint32_t)(b - a));
+      } else {
+        uint32_t len = o1 > o0 ? (uint32_t)(o1 - o0) : 0;
+        m = qk_like_match(&sp, bytes + o0, len);
+      }
+      out[r] = (uint8_t)m ^ neg;
+    }
+    if (staged) __syncthreads();  // tile is rewritten by the next span
+  }
+}
+
+// Which path a pattern takes when its spans fit the tile (measured,
+// profiles/like.md): a pattern with a searched segment reads most of every
+// row, and the LDS staging wins; a pattern of anchored segments only
+// (prefix, suffix, equality) touches a few bytes per row, and copying the
+// whole span into LDS first loses to reading those bytes directly.
+static bool qk_like_wants_stage(const qk_like_pat *p) {
+  uint32_t anchored = (p->anchor_start ? 1u : 0u) + (p->anchor_end ? 1u : 0u);
+  return p->nseg > anchored;
+}
+template <typename OffT>
+static int qk_str_like_impl(const char *who, void *stream, uint64_t n,
+                            const OffT *offsets, const uint8_t *bytes,
+                            const qk_like_pat *pat, int negate, bool stage,
+                            uint8_t *out_flags) {
+  if (!n) return 0;
+  if (pat->nseg > QK_LIKE_MAX_SEGS)
+    return qk_fail(who, hipErrorInvalidValue);
+  uint32_t blocks =
+      (uint32_t)qk_min_u64(4 * MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  if (stage)
+    hipLaunchKernelGGL((k_str_like<OffT, true>), dim3(blocks), dim3(BLOCK),
+                       0, (hipStream_t)stream, n, offsets, bytes, *pat,
+                       negate, out_flags);
+  else
+    hipLaunchKernelGGL((k_str_like<OffT, false>), dim3(blocks), dim3(BLOCK),
+                       0, (hipStream_t)stream, n, offsets, bytes, *pat,
+                       negate, out_flags);
+  QK_TRY(who, hipGetLastError());
+  return 0;
+}
+extern "C" int qk_str_like_i32(void *stream, uint64_t n,
+                               const int32_t *offsets, const uint8_t *bytes,
+                               const qk_like_pat *pat, int negate,
+                               uint8_t *out_flags) {
+  return qk_str_like_impl("qk_str_like_i32", stream, n, offsets, bytes, pat,
+                          negate, qk_like_wants_stage(pat), out_flags);
+}
+extern "C" int qk_str_like_i64(void *stream, uint64_t n,
+                               const int64_t *offsets, const uint8_t *bytes,
+                               const qk_like_pat *pat, int negate,
+                               uint8_t *out_flags) {
+  return qk_str_like_impl("qk_str_like_i64", stream, n, offsets, bytes, pat,
+                          negate, qk_like_wants_stage(pat), out_flags);
+}
+extern "C" int qk_str_like_path_i32(void *stream, uint64_t n,
+                                    const int32_t *offsets,
+                                    const uint8_t *bytes,
+                                    const qk_like_pat *pat, int negate,
+                                    int stage, uint8_t *out_flags) {
+  return qk_str_like_impl("qk_str_like_path_i32", stream, n, offsets, bytes,
+                          pat, negate, stage != 0, out_flags);
+}
+extern "C" int qk_str_like_path_i64(void *stream, uint64_t n,
+                                    const int64_t *offsets,
+                                    const uint8_t *bytes,
+                                    const qk_like_pat *pat, int negate,
+                                    int stage, uint8_t *out_flags) {
+  return qk_str_like_impl("qk_str_like_path_i64", stream, n, offsets, bytes,
+                          pat, negate, stage != 0, out_flags);
+}
+extern "C" int qk_str_like_host_i64(uint64_t n, const int64_t *offsets,
+                                    const uint8_t *bytes,
+                                    const qk_like_pat *pat, int negate,
+                                    uint8_t *out_flags) {
+  uint8_t neg = negate ? 1 : 0;
+  for (uint64_t r = 0; r < n; r++) {
+    int64_t o0 = offsets[r], o1 = offsets[r + 1];
+    uint32_t len = o1 > o0 ? (uint32_t)(o1 - o0) : 0;
+    out_flags[r] = (uint8_t)qk_like_match(pat, bytes + o0, len) ^ neg;
+  }
+  return 0;
+}
+extern "C" int qk_like_tile_bytes(void) { return QK_LIKE_TILE; }
+
 __global__ void __launch_bounds__(BLOCK) k_i64_combine(
     uint64_t n, const int64_t *__restrict__ x, const int64_t *__restrict__ y,
     int64_t scale, int64_t *__restrict__ out) {

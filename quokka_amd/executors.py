@@ -898,6 +898,16 @@ def gpu_partition_fn(data, source_channel, num_target_channels, key=None,
     with quokka_runtime.py:222) -> optional column projection (sorted
     order, core.py:191-193).
 
+    A predicate may name a free-text string column (one with no entry in
+    `string_dicts`) in `col LIKE 'pat'`, NOT LIKE, = 'lit', <> 'lit' and
+    != 'lit' — the reference's filter_sql("o_comment not like
+    '%special%requests%'") (apps/tpc-h/tpch.py:380) as written. Such a
+    column is staged from its Arrow offsets + bytes buffers
+    (ops.StringColumn) and matched per row on the device (ops.like); the
+    flags feed the JIT predicate like any other input, on the plain and
+    the batch_agg path alike. String columns the predicate does not name
+    never reach the device.
+
     batch_agg = (group_keys, aggs) with group_keys a list of
     (u8_code_column, cardinality) and aggs the two-phase PARTIAL forms
     ('SUM(expr) as x' / 'COUNT(*) as n', sql_utils.py:299-413). The
@@ -939,6 +949,19 @@ def gpu_partition_fn(data, source_channel, num_target_channels, key=None,
 
     host_cols = {c: _col(c) for c in data.column_names}
 
+    def _jit_schema(dcols):
+        """Device columns + every raw string column (object marker)."""
+        schema = {c: v.dtype for c, v in dcols.items()}
+        for c, v in host_cols.items():
+            if v.dtype == object and _is_stringish(data.column(c)):
+                schema[c] = np.dtype(object)
+        return schema
+
+    def _stage_raw_strings(prog, dcols):
+        """Upload the raw string columns `prog`'s predicate names."""
+        for c in sorted({t[1] for t in prog.str_terms}):
+            dcols[c] = ops.StringColumn.from_arrow(data.column(c))
+
     if batch_agg is not None:
         if transforms:
             raise ValueError("batch_agg already aggregates arbitrary "
@@ -955,9 +978,9 @@ def gpu_partition_fn(data, source_channel, num_target_channels, key=None,
                                  else ["COUNT(*) as __qk_presence"])
         dcols = {c: shim.DevColumn.from_numpy(v)
                  for c, v in host_cols.items() if v.dtype != object}
-        schema = {c: v.dtype for c, v in dcols.items()}
-        agg = jit.JitAggregate(schema, group_keys, run_aggs, predicate,
-                               string_dicts)
+        agg = jit.JitAggregate(_jit_schema(dcols), group_keys, run_aggs,
+                               predicate, string_dicts)
+        _stage_raw_strings(agg, dcols)
         acc = agg.make_acc()
         agg.run(dcols, acc)
         partials = agg.read(acc)               # (ngroups, naggs)
@@ -991,8 +1014,8 @@ def gpu_partition_fn(data, source_channel, num_target_channels, key=None,
         from . import jit
         dcols = {c: shim.DevColumn.from_numpy(v)
                  for c, v in host_cols.items() if v.dtype != object}
-        schema = {c: v.dtype for c, v in dcols.items()}
-        f = jit.JitFilter(predicate, schema, string_dicts)
+        f = jit.JitFilter(predicate, _jit_schema(dcols), string_dicts)
+        _stage_raw_strings(f, dcols)
         fidx, k = f.run(dcols)
         sel0 = fidx.to_numpy(k)
         host_cols = {c: v[sel0] for c, v in host_cols.items()}

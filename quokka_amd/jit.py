@@ -15,6 +15,13 @@ reference's TPC-H workload uses (apps/tpc-h/tpch.py filter_sql calls):
   (% = any run, _ = any char) is matched against the dictionary VALUES
   host-side and becomes a code-set test (no per-row string work on
   device — low-cardinality dictionaries make LIKE a set membership)
+  col LIKE 'pat' / NOT LIKE / = 'lit' / <> 'lit' / != 'lit' on a RAW
+  string column (schema dtype object, cols entry an ops.StringColumn):
+  each distinct (column, pattern, exact) becomes a string term that
+  ops.like evaluates on device into a u8 flag column; the predicate sees
+  it as one more input, `(vK) != 0` (or `== 0` for the negated forms), so
+  AND/OR/NOT and numeric terms compose around it unchanged. IN lists on
+  raw string columns are not supported.
   arithmetic   + - * / on columns and literals
   literals     ints, floats, date 'YYYY-MM-DD' (+/- interval 'N'
                day/month/year, evaluated host-side to date32 days),
@@ -40,6 +47,7 @@ from .shim import DevColumn, c_u64, c_vp
 _EPOCH = datetime.date(1970, 1, 1)
 _TYPE_CODE = {np.dtype(np.int32): 0, np.dtype(np.float64): 1,
               np.dtype(np.uint8): 2, np.dtype(np.int64): 3}
+RAW_STRING = np.dtype(object)   # schema marker: free-text string column
 
 _TOKEN = re.compile(r"""
     \s*(?:
@@ -123,6 +131,54 @@ class Translator:
         self.schema = schema            # name -> np dtype
         self.string_dicts = string_dicts or {}
         self.cols = []                  # referenced column names, in order
+        # raw-string terms: (flag column name, column, pattern, exact);
+        # each flag column is a synthetic u8 entry of self.cols
+        self.str_terms = []
+
+    def dtype_of(self, name):
+        """dtype of a self.cols entry (string-term flag columns are u8)."""
+        if any(t[0] == name for t in self.str_terms):
+            return np.dtype(np.uint8)
+        return np.dtype(self.schema[name])
+
+    def str_term_ref(self, col, pattern, exact):
+        """-> 'vK' of the flag column for this term; identical terms share
+        one."""
+        for name, c, p, e in self.str_terms:
+            if (c, p, e) == (col, pattern, exact):
+                return "v%d" % self.cols.index(name)
+        name = "__qk_like%d" % len(self.str_terms)
+        while name in self.schema:
+            name += "_"
+        self.str_terms.append((name, col, pattern, exact))
+        self.cols.append(name)
+        return "v%d" % self.cols.index(name)
+
+    def _p_raw_string(self, col):
+        """Comparison of a raw string column, after its identifier."""
+        t = self.peek()
+        neg = False
+        if t and t.kind == "NOT":
+            self.take()
+            neg = True
+            t = self.peek()
+        if t and t.kind == "LIKE":
+            self.take()
+            pat, exact = self.take("str").val, False
+        elif t and t.kind == "IN":
+            raise ValueError("IN list on raw string column %r is not "
+                             "supported" % col)
+        elif t and not neg and t.kind == "op" and \
+                t.val in ("=", "==", "!=", "<>"):
+            self.take()
+            neg = t.val in ("!=", "<>")
+            pat, exact = self.take("str").val, True
+        else:
+            raise ValueError("raw string column %r supports only LIKE, "
+                             "NOT LIKE, =, <> and != with a string "
+                             "literal" % col)
+        ref = self.str_term_ref(col, pat, exact)
+        raise _Folded("(%s) %s 0" % (ref, "==" if neg else "!="))
 
     def col_ref(self, name):
         if name not in self.schema:
@@ -311,6 +367,8 @@ class Translator:
         if t.kind == "str":
             return t.val, "strlit"   # resolved by comparison partner
         if t.kind == "ident":
+            if t.val in self.schema and self.schema[t.val] == RAW_STRING:
+                self._p_raw_string(t.val)      # raises _Folded
             ref, dtype = self.col_ref(t.val)
             # string equality: partner literal becomes the dict code
             nxt = self.peek()
@@ -405,6 +463,29 @@ def translate(predicate, schema, string_dicts=None):
     return tr.translate(predicate), tr.cols
 
 
+def translate_terms(predicate, schema, string_dicts=None):
+    """translate() plus the raw-string terms: -> (c_expr, columns,
+    str_terms). Each term is (flag_column, column, pattern, exact); its
+    flag column is a synthetic u8 entry of `columns` that ops.like fills
+    at run time."""
+    tr = Translator(schema, string_dicts)
+    return tr.translate(predicate), tr.cols, tr.str_terms
+
+
+def _eval_str_terms(str_terms, cols, stream):
+    """Run each string term's LIKE kernel -> {flag column: DevColumn u8}."""
+    from . import ops
+    flags = {}
+    for name, col, pattern, exact in str_terms:
+        sc = cols[col]
+        if not isinstance(sc, ops.StringColumn):
+            raise TypeError("column %r is a raw string in the schema: "
+                            "cols[%r] must be an ops.StringColumn"
+                            % (col, col))
+        flags[name] = ops.like(sc, pattern, exact=exact, stream=stream)
+    return flags
+
+
 def translate_arith(expr, schema, translator=None):
     """Arithmetic expression (no comparisons) -> (c_expr, columns)."""
     tr = translator or Translator(schema)
@@ -471,7 +552,8 @@ class JitAggregate:
             self.agg_names.append(alias or a.strip())
         self.naggs = len(agg_exprs)
         self.cols = tr.cols
-        self.dtypes = [np.dtype(schema[c]) for c in self.cols]
+        self.str_terms = tr.str_terms
+        self.dtypes = [tr.dtype_of(c) for c in self.cols]
 
         lib = shim._lib
         lib.qk_jit_agg_build.argtypes = [
@@ -514,10 +596,19 @@ class JitAggregate:
         lib = shim._lib
         lib.qk_jit_agg_run.argtypes = [c_vp, c_vp, c_u64,
                                        ctypes.POINTER(c_vp), c_vp]
+        flags = _eval_str_terms(self.str_terms, cols, stream)
+        if flags:
+            cols = dict(cols, **flags)
         n = cols[self.cols[0]].n
         ptrs = (c_vp * len(self.cols))(*[cols[c].ptr for c in self.cols])
         sh = stream.handle if stream else None
         rc = lib.qk_jit_agg_run(self.prog, sh, c_u64(n), ptrs, acc.ptr)
+        if flags:
+            # the flag columns go back to the pool: the kernel reading
+            # them must have finished first
+            shim.call("qk_stream_sync", sh)
+            for f in flags.values():
+                f.free()
         if rc != 0:
             raise shim.QkError("jit agg run failed: %s"
                                % lib.qk_jit_last_error().decode())
@@ -583,8 +674,10 @@ class JitFilter:
     """Compiled fused filter for one predicate over a fixed schema."""
 
     def __init__(self, predicate, schema, string_dicts=None):
-        self.expr, self.cols = translate(predicate, schema, string_dicts)
-        self.dtypes = [np.dtype(schema[c]) for c in self.cols]
+        tr = Translator(schema, string_dicts)
+        self.expr = tr.translate(predicate)
+        self.cols, self.str_terms = tr.cols, tr.str_terms
+        self.dtypes = [tr.dtype_of(c) for c in self.cols]
         types = (ctypes.c_int * len(self.cols))(
             *[_TYPE_CODE[d] for d in self.dtypes])
         prog = c_vp(0)
@@ -602,8 +695,12 @@ class JitFilter:
 
     def run(self, cols, stream=None):
         """cols: dict name -> DevColumn (must include every referenced
-        column, all same length). Returns (idx DevColumn u32, count)."""
+        column, all same length; an ops.StringColumn for each raw string
+        column). Returns (idx DevColumn u32, count)."""
         from . import ops
+        flags = _eval_str_terms(self.str_terms, cols, stream)
+        if flags:
+            cols = dict(cols, **flags)
         n = cols[self.cols[0]].n
         ptrs = (c_vp * len(self.cols))(
             *[cols[c].ptr for c in self.cols])
@@ -616,12 +713,16 @@ class JitFilter:
         rc = lib.qk_jit_filter_run(self.prog, sh, c_u64(n), ptrs, idx.ptr,
                                    cnt.ptr)
         if rc != 0:
+            for f in flags.values():
+                f.free()
             raise shim.QkError("jit run failed: %s"
                                % lib.qk_jit_last_error().decode())
         if stream:
             stream.sync()
         k = ops._read_u64(cnt)
         cnt.free()
+        for f in flags.values():
+            f.free()
         idx.n = k
         return idx, k
 

@@ -497,6 +497,73 @@ class DeviceStringDict:
         self._ctr.free()
 
 
+class StringColumn:
+    """Device-resident Arrow string column: `offsets` (DevColumn i32 or
+    i64, n+1 entries starting at 0) + `data` (DevBuffer of the string
+    bytes). The free-text columns the reference filters with LIKE inside
+    DuckDB/polars (apps/tpc-h/tpch.py:380 o_comment, :413 s_comment, :316
+    p_name) live on the device in this form."""
+
+    def __init__(self, offsets, data, n):
+        self.offsets = offsets
+        self.data = data
+        self.n = int(n)
+
+    @classmethod
+    def from_arrow(cls, col):
+        """pyarrow string / large_string / dictionary-of-string Array or
+        ChunkedArray -> StringColumn. The Arrow offsets and data buffers
+        are uploaded as they are (no per-row host work); a sliced array
+        uploads only the bytes its rows cover."""
+        import pyarrow as pa
+        if isinstance(col, pa.ChunkedArray):
+            col = col.combine_chunks()
+        if pa.types.is_dictionary(col.type):
+            col = col.dictionary_decode() if hasattr(col, "dictionary_decode") \
+                else col.cast(col.type.value_type)
+        large = pa.types.is_large_string(col.type)
+        if not (large or pa.types.is_string(col.type)):
+            raise TypeError("StringColumn.from_arrow: not a string column "
+                            "(%s)" % col.type)
+        if col.null_count:
+            raise TypeError("null strings unsupported")
+        n = len(col)
+        odt = np.int64 if large else np.int32
+        bufs = col.buffers()
+        if n == 0 or bufs[1] is None:
+            off = np.zeros(n + 1, dtype=odt)
+        else:
+            off = np.frombuffer(bufs[1], dtype=odt,
+                                count=col.offset + n + 1)[col.offset:]
+        lo, hi = int(off[0]), int(off[-1])
+        if lo:
+            off = off - odt(lo)
+        data = DevBuffer(hi - lo)
+        if hi > lo:
+            raw = np.frombuffer(bufs[2], dtype=np.uint8, count=hi)[lo:]
+            shim._bounce.h2d(data.ptr, raw)
+        return cls(DevColumn.from_numpy(off), data, n)
+
+    def free(self):
+        self.offsets.free()
+        self.data.free()
+
+
+def like(strcol, pattern, negate=False, exact=False, stream=None):
+    """Per-row SQL LIKE over a StringColumn -> DevColumn u8 of 0/1 flags
+    (DuckDB's default semantics: case-sensitive, % any run, _ one UTF-8
+    code point, no ESCAPE). exact=True is string equality: every pattern
+    byte literal. negate=True gives NOT LIKE / <>."""
+    pat = shim.like_compile(pattern, exact)
+    out = DevColumn(np.uint8, strcol.n)
+    fn = "qk_str_like_i64" if strcol.offsets.dtype == np.dtype(np.int64) \
+        else "qk_str_like_i32"
+    sh = stream.handle if stream else None
+    shim.call(fn, sh, c_u64(strcol.n), strcol.offsets.ptr, strcol.data.ptr,
+              ctypes.byref(pat), int(bool(negate)), out.ptr)
+    return out
+
+
 def sort_permutation(col, stream=None, descending=False):
     """Stable sort permutation of a DevColumn (i64/f64/i32/u32 keys):
     returns a u32 DevColumn `perm` with rows in ascending (or descending)

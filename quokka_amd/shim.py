@@ -140,6 +140,14 @@ _SIGS = {
                            c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "qk_str_dict_rehash": [c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp,
                            c_u64],
+    "qk_str_like_i32": [c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.c_int, c_vp],
+    "qk_str_like_i64": [c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.c_int, c_vp],
+    "qk_str_like_path_i32": [c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.c_int,
+                             ctypes.c_int, c_vp],
+    "qk_str_like_path_i64": [c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.c_int,
+                             ctypes.c_int, c_vp],
+    "qk_str_like_host_i64": [c_u64, c_vp, c_vp, c_vp, ctypes.c_int, c_vp],
+    "qk_like_compile": [c_vp, c_u32, ctypes.c_int, c_vp],
     "qk_d2d": [c_vp, c_vp, c_u64],
     "qk_i64_combine": [c_vp, c_u64, c_vp, c_vp, c_i64, c_vp],
     "qk_i64_shr": [c_vp, c_u64, c_vp, ctypes.c_int, c_vp],
@@ -183,6 +191,38 @@ def device_count():
 
 
 JOIN_EMPTY = np.int64(-(2 ** 63))  # QK_JOIN_EMPTY
+
+LIKE_MAX_PAT = 256   # QK_LIKE_MAX_PAT
+LIKE_MAX_SEGS = 16   # QK_LIKE_MAX_SEGS
+# LDS tile of qk_str_like_*: a 256-row block whose byte span fits it is
+# staged through LDS, a longer one is matched from global memory
+LIKE_TILE = int(_lib.qk_like_tile_bytes())
+
+
+class LikePat(ctypes.Structure):
+    """qk_like_pat (include/quokka_amd.h): the compiled LIKE pattern."""
+    _fields_ = [("nseg", c_u32), ("anchor_start", c_u8),
+                ("anchor_end", c_u8), ("exact", c_u8), ("pad_", c_u8),
+                ("seg_off", ctypes.c_uint16 * LIKE_MAX_SEGS),
+                ("seg_len", ctypes.c_uint16 * LIKE_MAX_SEGS),
+                ("wild", c_u32 * (LIKE_MAX_PAT // 32)),
+                ("pat", c_u8 * LIKE_MAX_PAT)]
+
+
+assert ctypes.sizeof(LikePat) == 360
+
+
+def like_compile(pattern, exact=False):
+    """SQL LIKE pattern (str or bytes) -> LikePat. Patterns beyond the
+    struct's bounds raise ValueError (never truncated)."""
+    raw = pattern.encode() if isinstance(pattern, str) else bytes(pattern)
+    out = LikePat()
+    rc = _lib.qk_like_compile(raw, c_u32(len(raw)), int(bool(exact)),
+                              ctypes.byref(out))
+    if rc != 0:
+        raise ValueError(_lib.qk_last_error().decode())
+    return out
+
 
 class _PinnedBounce:
     """Double-buffered pinned bounce for pageable h2d/d2h copies (PCIe
