@@ -136,6 +136,12 @@ int qk_q1_agg(void *stream, uint64_t n,
               const double *l_tax, const uint8_t *l_returnflag,
               const uint8_t *l_linestatus, int32_t cutoff_date,
               double *out_dev /* f64[48] */);
+/* Shape of the qk_q1_agg streaming kernel, for tests that need its edges:
+ * rows per block tile (returns the size, not an error code), and the
+ * number of blocks of one launch over a large input on the current device
+ * (blocks x tile rows = rows of one full grid sweep). */
+int qk_q1_tile_rows(void);
+int qk_q1_grid_blocks(int *out);
 
 /* ---- TPC-H Q6: fused filter + sum ------------------------------------ *
  * tpch_ref.py:171-183 semantics. out_dev = f64[2] {sum_revenue, count};
