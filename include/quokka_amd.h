@@ -142,6 +142,14 @@ int qk_q1_agg(void *stream, uint64_t n,
  * (blocks x tile rows = rows of one full grid sweep). */
 int qk_q1_tile_rows(void);
 int qk_q1_grid_blocks(int *out);
+/* Launch shape of the generic operators (sort, partition, join, group-by),
+ * for tests that need its edges: threads per block and the block cap of one
+ * launch (both return the size, not an error code). Up to
+ * qk_block_threads() * qk_max_blocks() rows qk_sort_pairs_u64 and
+ * qk_partition_scatter give each block one tile of qk_block_threads() rows;
+ * above it a block loops over several tiles. */
+int qk_block_threads(void);
+int qk_max_blocks(void);
 
 /* ---- TPC-H Q6: fused filter + sum ------------------------------------ *
  * tpch_ref.py:171-183 semantics. out_dev = f64[2] {sum_revenue, count};
@@ -194,7 +202,14 @@ int qk_gather_u8(void *stream, uint64_t n_idx, const uint32_t *idx,
  * through chain_next. slot_keys must be pre-filled with QK_JOIN_EMPTY
  * (qk_fill_i64), slot_head with -1 bytes (qk_dmemset 0xff).
  * Build may be called repeatedly (batch accumulation): build_row_offset is
- * added to local row indices so chains index the concatenated build side. */
+ * added to local row indices so chains index the concatenated build side.
+ * PRECONDITION: QK_JOIN_EMPTY marks a free slot, so no BUILD key (and no
+ * group key of qk_groupby_i64_sum) may equal it: such a row would match the
+ * first free slot without claiming it, and a later key that claims the slot
+ * inherits its chain (or its sums). The kernels do not check; callers with
+ * host keys reject it before staging (quokka_amd.ops.check_no_sentinel_key).
+ * PROBE keys may take any value: a probe for QK_JOIN_EMPTY stops at the
+ * first free slot, whose head is -1, and reports no match. */
 #define QK_JOIN_EMPTY INT64_MIN
 int qk_join_build(void *stream, uint64_t n_build, const int64_t *keys,
                   uint32_t build_row_offset, int64_t *slot_keys,
@@ -318,7 +333,8 @@ int qk_q5_probe_agg_nt(void *stream, uint64_t n, const int64_t *l_orderkey,
  * Replaces SQLAggExecutor's DuckDB group-by (sql_executors.py:592-599) for
  * distributive SUM over an i64 key (the post-rewrite partial form,
  * sql_utils.py:299-413). Open-addressing accumulate table; slot_keys
- * pre-filled with QK_JOIN_EMPTY, slot_sums zeroed. Repeated calls
+ * pre-filled with QK_JOIN_EMPTY (so no key may equal it, see
+ * QK_JOIN_EMPTY above), slot_sums zeroed. Repeated calls
  * accumulate. nvals value columns share one key lookup (vals/slot_sums are
  * arrays-of-columns, each `capacity` doubles: slot_sums[c*capacity+slot]). */
 /* agg_ops_dev (device i32[nvals], nullable -> all SUM): per value column
@@ -357,7 +373,10 @@ int qk_groupby_extract_gt(void *stream, const int64_t *table, int rstride,
 /* ---- hash partition (shuffle map side) -------------------------------- *
  * Replaces partition_key_str (quokka_runtime.py:217-231). Int key semantics
  * bit-exact with the reference (:222): part = key % nparts (non-negative
- * keys). hist_dev: u64[nparts], zeroed. */
+ * keys; a negative key takes the mathematical, non-negative mod).
+ * hist_dev: u64[nparts], zeroed. nparts == 0 is refused with
+ * hipErrorInvalidValue before any launch, by both entry points;
+ * qk_partition_scatter also refuses nparts > 512. */
 int qk_partition_hist(void *stream, uint64_t n, const int64_t *keys,
                       uint32_t nparts, uint64_t *hist_dev);
 /* Scatter row indices grouped by partition: out_idx[offsets[p] ... ] = rows
@@ -377,6 +396,10 @@ int qk_partition_scatter(void *stream, uint64_t n, const int64_t *keys,
 int qk_sort_pairs_u64(void *stream, uint64_t n, uint64_t *keys,
                       uint32_t *payload, uint64_t *keys_tmp,
                       uint32_t *pay_tmp, int npasses);
+/* f64 image order: -inf < ... < -0.0 < +0.0 < ... < +inf < NaN. Every NaN,
+ * of either sign and any payload, maps to UINT64_MAX: NaNs sort last
+ * ascending, first descending (after qk_bnot_u64), and keep their input
+ * order among themselves. */
 int qk_map_f64_u64(void *stream, uint64_t n, const double *in, uint64_t *out);
 int qk_map_i64_u64(void *stream, uint64_t n, const int64_t *in,
                    uint64_t *out);
@@ -630,7 +653,9 @@ int qk_pq_walk_pages(const uint8_t *buf, uint64_t start,
 /* Range-partition ids (quokka_runtime.py:234-243 partition_key_range):
  * id = (key - 1) / (total_range / nparts), floor division, clamped into
  * [0, nparts-1] (the reference misroutes keys outside [1, total_range];
- * we clamp — documented divergence, same key->same channel). Feed the
+ * we clamp — documented divergence, same key->same channel). Every key
+ * <= 0, INT64_MIN included, gives id 0, so ids never decrease as the key
+ * grows. Feed the
  * ids to qk_partition_hist/scatter (id % nparts == id). */
 int qk_range_part_ids(void *stream, uint64_t n, const int64_t *keys,
                       int64_t per_range, uint32_t nparts, int64_t *out);

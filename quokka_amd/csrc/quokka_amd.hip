@@ -631,6 +631,8 @@ static int q1_resident_blocks(int *out) {
 }
 
 extern "C" int qk_q1_tile_rows(void) { return Q1_TILE; }
+extern "C" int qk_block_threads(void) { return BLOCK; }
+extern "C" int qk_max_blocks(void) { return MAX_BLOCKS; }
 extern "C" int qk_q1_grid_blocks(int *out) { return q1_resident_blocks(out); }
 
 extern "C" int qk_q1_agg(void *stream, uint64_t n, const int32_t *shipdate,
@@ -2343,14 +2345,18 @@ __global__ void k_reduce_max_u64(uint64_t n, const uint64_t *__restrict__ in,
 }
 
 // order-preserving key maps: sort ascending on the u64 image == ascending
-// on the source type
+// on the source type (f64: -0.0 < +0.0, NaN greatest)
 __global__ void k_map_f64_u64(uint64_t n, const double *__restrict__ in,
                               uint64_t *__restrict__ out) {
   uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
-    uint64_t b = (uint64_t)__double_as_longlong(in[i]);
-    out[i] = (b & 0x8000000000000000ULL) ? ~b : (b | 0x8000000000000000ULL);
+    double v = in[i];
+    uint64_t b = (uint64_t)__double_as_longlong(v);
+    uint64_t m = (b & 0x8000000000000000ULL) ? ~b : (b | 0x8000000000000000ULL);
+    // every NaN (either sign, any payload) takes the greatest image: NaNs
+    // sort last ascending, first after qk_bnot_u64, stable among themselves
+    out[i] = v != v ? ~0ULL : m;
   }
 }
 __global__ void k_map_i64_u64(uint64_t n, const int64_t *__restrict__ in,
@@ -3748,10 +3754,10 @@ __global__ void __launch_bounds__(BLOCK) k_range_part_ids(
   uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i < n; i += stride) {
-    int64_t k = keys[i] - 1;
-    int64_t q = k / per_range;
-    if (k % per_range < 0) q--;               // floor division
-    if (q < 0) q = 0;
+    // keys <= 0 clamp to range 0 without forming key - 1, which overflows
+    // for INT64_MIN; for key >= 1 the dividend is non-negative
+    int64_t k = keys[i];
+    int64_t q = k <= 0 ? 0 : (k - 1) / per_range;
     if (q >= (int64_t)nparts) q = (int64_t)nparts - 1;
     out[i] = q;
   }
@@ -4221,6 +4227,8 @@ __global__ void __launch_bounds__(BLOCK) k_partition_hist(
 extern "C" int qk_partition_hist(void *stream, uint64_t n, const int64_t *keys,
                                  uint32_t nparts, uint64_t *hist) {
   if (!n) return 0;
+  if (!nparts)  // key % 0 on the device would index LDS with garbage
+    return qk_fail("qk_partition_hist.nparts", hipErrorInvalidValue);
   uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
   hipLaunchKernelGGL(k_partition_hist, dim3(blocks), dim3(BLOCK),
                      nparts * sizeof(uint32_t), (hipStream_t)stream, n, keys,
@@ -4269,7 +4277,7 @@ extern "C" int qk_partition_scatter(void *stream, uint64_t n,
                                     const int64_t *keys, uint32_t nparts,
                                     uint64_t *cursors, uint32_t *out_idx) {
   if (!n) return 0;
-  if (nparts > 512)
+  if (!nparts || nparts > 512)
     return qk_fail("qk_partition_scatter.nparts", hipErrorInvalidValue);
   uint64_t chunk = (n + MAX_BLOCKS - 1) / MAX_BLOCKS;
   chunk = ((chunk + BLOCK - 1) / BLOCK) * BLOCK;

@@ -175,6 +175,9 @@ class GPUBuildProbeJoinExecutor(Executor):
             else:
                 raise TypeError("GPU join requires integer or string keys,"
                                 " got %s" % keys.dtype)
+        if self._key_dict is None:      # dictionary codes are >= 0
+            ops.check_no_sentinel_key(keys, type(self).__name__,
+                                      self.right_on)
         n = len(keys)
         self._table = ops.JoinTable(max(16, n))
         if n:
@@ -421,6 +424,9 @@ class GPUAggExecutor(Executor):
             self._key_state["mode"] = "passthrough"
             self._key_state["pass_dict"] = self._key_state["dicts"].get(
                 self.groupby_keys[0])
+            if self._key_state["pass_dict"] is None:  # codes are >= 0
+                ops.check_no_sentinel_key(arrs[0], type(self).__name__,
+                                          self.groupby_keys[0])
             return arrs[0]
         # composite: each non-i64 key coded via np codebook, packed base-N
         self._key_state["mode"] = "composite"
@@ -631,6 +637,13 @@ class GPUDiskBuildProbeJoinExecutor(Executor):
         batch = pa.concat_tables(batches)
         if stream_id == 1:                       # build: spill the chunk
             assert self.phase == "build"
+            import pyarrow.types as pat
+            bcol = batch.column(self.right_on)
+            if pat.is_integer(bcol.type):
+                from . import ops
+                ops.check_no_sentinel_key(
+                    bcol.to_numpy().astype(np.int64),
+                    type(self).__name__, self.right_on)
             t = batch.cast(pa.schema([pa.field(f.name, f.type,
                                                nullable=False)
                                       for f in batch.schema]))
@@ -745,6 +758,8 @@ class GPUDistinctExecutor(Executor):
             else:
                 raise TypeError("GPUDistinctExecutor requires integer or "
                                 "string keys, got %s" % keys.dtype)
+        if self._key_dict is None:      # dictionary codes are >= 0
+            ops.check_no_sentinel_key(keys, type(self).__name__, self.keys)
         # within-batch unique (first occurrence), as batch.unique() does
         _, first_idx = np.unique(keys, return_index=True)
         first_idx.sort()

@@ -81,6 +81,22 @@ def q6_agg(n, shipdate, qty, price, disc, date_lo, date_hi, disc_lo, disc_hi,
               ctypes.c_double(qty_hi), out_buf.ptr)
 
 
+def check_no_sentinel_key(keys, operator, column):
+    """Raise ValueError when the host i64 key array `keys` contains
+    INT64_MIN. That value is QK_JOIN_EMPTY, the free-slot marker of the
+    join and group-by tables: a build or group key equal to it matches the
+    first free slot without claiming it, and a later key inherits its chain
+    or its sums. Host-only, so executors call it before any device call.
+    Join PROBE keys need no check (a probe for it reports no match)."""
+    keys = np.asarray(keys)
+    if keys.size and keys.dtype == np.int64 and \
+            bool((keys == shim.JOIN_EMPTY).any()):
+        raise ValueError(
+            "%s: key column %r contains INT64_MIN (%d), the reserved "
+            "empty-slot marker of the device hash table; such keys are "
+            "not supported" % (operator, column, int(shim.JOIN_EMPTY)))
+
+
 def _pow2_at_least(n):
     c = 1
     while c < n:
@@ -91,7 +107,12 @@ def _pow2_at_least(n):
 class JoinTable:
     """Device hash-join state = BuildProbeJoinExecutor's vstacked build side
     (sql_executors.py:346-374). build() may be called per build batch;
-    probe() per probe batch."""
+    probe() per probe batch.
+
+    Precondition: no BUILD key equals INT64_MIN (QK_JOIN_EMPTY, the
+    free-slot marker). build() takes device keys and does not look at
+    them; callers with host keys use check_no_sentinel_key first. Probe
+    keys may take any value."""
 
     def __init__(self, expected_build_rows, stream=None):
         self.cap = _pow2_at_least(max(16, 2 * int(expected_build_rows)))
@@ -160,7 +181,11 @@ class JoinTable:
 class GroupByI64:
     """Device group-by accumulate table over an i64 key with nvals f64 SUM
     columns (SQLAggExecutor's post-rewrite distributive form,
-    sql_utils.py:299-413). update() per batch, extract() at done()."""
+    sql_utils.py:299-413). update() per batch, extract() at done().
+
+    Precondition: no key equals INT64_MIN (QK_JOIN_EMPTY, the free-slot
+    marker). update() takes device keys and does not look at them;
+    callers with host keys use check_no_sentinel_key first."""
 
     AGG_INIT = {0: 0.0, 1: float("inf"), 2: float("-inf")}  # SUM/MIN/MAX
 

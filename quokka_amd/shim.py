@@ -192,6 +192,12 @@ def device_count():
 
 JOIN_EMPTY = np.int64(-(2 ** 63))  # QK_JOIN_EMPTY
 
+# launch shape of the generic operators: up to BLOCK_THREADS * MAX_BLOCKS
+# rows the sort and the partition scatter give each block one tile, above
+# it a block loops over several tiles
+BLOCK_THREADS = int(_lib.qk_block_threads())
+MAX_BLOCKS = int(_lib.qk_max_blocks())
+
 LIKE_MAX_PAT = 256   # QK_LIKE_MAX_PAT
 LIKE_MAX_SEGS = 16   # QK_LIKE_MAX_SEGS
 # LDS tile of qk_str_like_*: a 256-row block whose byte span fits it is

@@ -34,7 +34,7 @@ def test_header_declares_expected_surface():
     assert len(syms) >= 30
     for must in ("qk_q1_agg", "qk_q6_agg", "qk_join_build", "qk_join_probe",
                  "qk_groupby_i64_sum", "qk_partition_hist", "qk_filter_i32",
-                 "qk_gen_lineitem"):
+                 "qk_gen_lineitem", "qk_block_threads", "qk_max_blocks"):
         assert must in syms
 
 
