@@ -23,6 +23,17 @@ static __host__ __device__ inline uint64_t qk_min_u64(uint64_t a, uint64_t b) {
 #define BLOCK 256
 #define MAX_BLOCKS 2048
 
+// Grid for a grid-stride kernel over work_items (rows, pairs, slots ...):
+// one thread per item up to MAX_BLOCKS blocks, never an empty grid — the
+// kernels that fold a tail into block 0 need that block even when
+// work_items rounds down to 0.
+static uint32_t qk_grid(uint64_t work_items) {
+  uint64_t b = qk_min_u64(MAX_BLOCKS, (work_items + BLOCK - 1) / BLOCK);
+  return b ? (uint32_t)b : 1u;
+}
+// hash-table capacities must be powers of two (slot = hash & (cap - 1))
+static bool qk_pow2(uint64_t v) { return (v & (v - 1)) == 0; }
+
 static __thread char g_err[512] = "";
 static __thread int g_err_set = 0;
 
@@ -100,7 +111,7 @@ __global__ void k_fill_i64(int64_t *dst, int64_t v, uint64_t n) {
 }
 extern "C" int qk_fill_i64(void *stream, int64_t *dst, int64_t v, uint64_t n) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_fill_i64, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, dst, v, n);
   QK_TRY("qk_fill_i64", hipGetLastError());
@@ -264,7 +275,7 @@ extern "C" int qk_gen_lineitem(void *stream, uint64_t n, uint64_t row_offset,
                                int32_t *l_shipdate, int32_t *l_commitdate,
                                int32_t *l_receiptdate) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_gen_lineitem, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, row_offset, seed, n_parts,
                      n_suppliers, n_orders, l_orderkey, l_suppkey, l_quantity,
@@ -332,7 +343,7 @@ extern "C" int qk_gen_orders(void *stream, uint64_t n, uint64_t row_offset,
                              uint8_t *o_orderpriority, double *o_totalprice,
                              int64_t li_n_parts) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_gen_orders, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, row_offset, seed, n_customers,
                      o_orderkey, o_custkey, o_orderdate, o_shippriority,
@@ -359,7 +370,7 @@ extern "C" int qk_gen_customer(void *stream, uint64_t n, uint64_t row_offset,
                                uint64_t seed, int64_t *c_custkey,
                                uint8_t *c_mktsegment, int32_t *c_nationkey) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_gen_customer, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, row_offset, seed, c_custkey,
                      c_mktsegment, c_nationkey);
@@ -397,6 +408,33 @@ extern "C" int qk_gen_customer(void *stream, uint64_t n, uint64_t row_offset,
 __device__ inline double wave_reduce(double v) {
   for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off);
   return v;
+}
+// wave total of a per-lane count, valid in lane 0
+__device__ inline uint32_t wave_sum(uint32_t v) {
+  for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off);
+  return v;
+}
+// Block total of a per-thread count: wave shuffle, one LDS word per wave,
+// thread 0 adds them. Thread 0 gets the total, every other thread gets 0.
+// Holds a __syncthreads(), so a block calls it with all of its threads or
+// none: at most once per kernel, outside divergent control flow. A guard
+// that is uniform over the grid (`if (match_count)` on a kernel argument)
+// keeps that legal.
+__device__ inline uint64_t block_sum(uint32_t mine) {
+  __shared__ uint32_t lds[BLOCK / WAVE];
+  mine = wave_sum(mine);
+  int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+  if (lane == 0) lds[wid] = mine;
+  __syncthreads();
+  uint64_t t = 0;
+  if (threadIdx.x == 0)
+    for (int w = 0; w < BLOCK / WAVE; w++) t += lds[w];
+  return t;
+}
+// block_sum, then ONE global atomic per block, and none for a zero total
+__device__ inline void block_add_count(uint32_t mine, uint64_t *dst) {
+  uint64_t t = block_sum(mine);
+  if (t) atomicAdd((unsigned long long *)dst, (unsigned long long)t);
 }
 
 // Row-pair grid-stride kernel: the path for column pointers that miss the
@@ -646,10 +684,7 @@ extern "C" int qk_q1_agg(void *stream, uint64_t n, const int32_t *shipdate,
                   ((uintptr_t)shipdate & 7) |
                   (((uintptr_t)rflag | (uintptr_t)lstat) & 1);
   if (mis) {
-    uint64_t npairs = n / 2;
-    uint32_t blocks =
-        (uint32_t)qk_min_u64(MAX_BLOCKS, (npairs + BLOCK - 1) / BLOCK);
-    if (!blocks) blocks = 1;
+    uint32_t blocks = qk_grid(n / 2);
     hipLaunchKernelGGL(k_q1_agg_rowpair, dim3(blocks), dim3(BLOCK), 0,
                        (hipStream_t)stream, n, shipdate, quantity, extprice,
                        discount, tax, rflag, lstat, cutoff, out);
@@ -731,10 +766,7 @@ extern "C" int qk_q6_agg(void *stream, uint64_t n, const int32_t *shipdate,
                          const double *discount, int32_t date_lo,
                          int32_t date_hi, double disc_lo, double disc_hi,
                          double qty_hi, double *out) {
-  uint64_t npairs = n / 2;
-  uint32_t blocks =
-      (uint32_t)qk_min_u64(MAX_BLOCKS, (npairs + BLOCK - 1) / BLOCK);
-  if (!blocks) blocks = 1;
+  uint32_t blocks = qk_grid(n / 2);
   hipLaunchKernelGGL(k_q6_agg, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, shipdate, quantity, extprice,
                      discount, date_lo, date_hi, disc_lo, disc_hi, qty_hi, out);
@@ -768,17 +800,8 @@ __global__ void __launch_bounds__(BLOCK) k_filter_count(
   uint32_t cnt = 0;
   for (uint64_t r = lo + threadIdx.x; r < hi; r += BLOCK)
     cnt += cmp_op(col[r], op, ref) ? 1u : 0u;
-  // wave reduce then block reduce
-  __shared__ uint32_t lds[BLOCK / WAVE];
-  for (int off = WAVE / 2; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
-  int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  if (lane == 0) lds[wid] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t s = 0;
-    for (int w = 0; w < BLOCK / WAVE; w++) s += lds[w];
-    block_counts[blockIdx.x] = s;
-  }
+  uint64_t s = block_sum(cnt);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = s;
 }
 
 __global__ void k_scan_blocks(uint64_t nblocks, uint64_t *__restrict__ counts,
@@ -886,7 +909,7 @@ __global__ void k_flag_gt_i32(uint64_t n, const int32_t *__restrict__ a,
 extern "C" int qk_flag_gt_i32(void *stream, uint64_t n, const int32_t *a,
                               const int32_t *b, double *out) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_flag_gt_i32, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, a, b, out);
   QK_TRY("qk_flag_gt_i32", hipGetLastError());
@@ -905,7 +928,7 @@ __global__ void k_mul_1md(uint64_t n, const double *__restrict__ a,
 extern "C" int qk_mul_1md(void *stream, uint64_t n, const double *a,
                           const double *b, double *out) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_mul_1md, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, a, b, out);
   QK_TRY("qk_mul_1md", hipGetLastError());
@@ -925,7 +948,7 @@ template <typename T>
 static int qk_gather_impl(const char *who, void *stream, uint64_t n,
                           const uint32_t *idx, const T *src, T *dst) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_gather<T>, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, idx, src, dst);
   QK_TRY(who, hipGetLastError());
@@ -958,6 +981,52 @@ __device__ inline uint64_t slot_of(int64_t key, uint64_t cap) {
   return splitmix64((uint64_t)key) & (cap - 1);
 }
 
+// THE find-or-insert walk of the join and Q3/Q5 tables (i64 key array):
+// returns the slot that holds `key`, claiming a free one (QK_JOIN_EMPTY ->
+// key, one CAS) when the key is new. The caller keeps the table below
+// full, or the walk never ends; a key equal to QK_JOIN_EMPTY matches the
+// first free slot without claiming it (ops.check_no_sentinel_key). The
+// group-by's strided-record twin of this loop lives in k_groupby_sum.
+__device__ inline uint64_t ht_find_or_insert(int64_t *slot_keys, uint64_t cap,
+                                             int64_t key) {
+  uint64_t s = slot_of(key, cap);
+  for (;;) {
+    int64_t cur = slot_keys[s];
+    if (cur == key) break;
+    if (cur == QK_JOIN_EMPTY) {
+      int64_t prev = (int64_t)atomicCAS((unsigned long long *)&slot_keys[s],
+                                        (unsigned long long)QK_JOIN_EMPTY,
+                                        (unsigned long long)key);
+      if (prev == QK_JOIN_EMPTY || prev == key) break;
+    }
+    s = (s + 1) & (cap - 1);
+  }
+  return s;
+}
+
+// THE lookup walk of the same tables, whose slots each carry one i32
+// (build row, chain head or value; never negative once built): the i32 of
+// the slot that holds `key`, and the slot itself in *slot_out (may be
+// NULL), or -1 once a free slot shows that the key is absent. The i32 is
+// loaded inside the walk, at the hit: a walk that only returned the slot
+// and left the load to its caller was tried, and cost every probe kernel
+// 2-4 VGPRs and the Q5 probe 1% of its rate.
+__device__ inline int32_t probe_unique(const int64_t *__restrict__ slot_keys,
+                                       const int32_t *__restrict__ slot_head,
+                                       uint64_t cap, int64_t key,
+                                       uint64_t *slot_out) {
+  uint64_t s = slot_of(key, cap);
+  for (;;) {
+    int64_t cur = slot_keys[s];
+    if (cur == key) {
+      if (slot_out) *slot_out = s;
+      return slot_head[s];
+    }
+    if (cur == QK_JOIN_EMPTY) return -1;
+    s = (s + 1) & (cap - 1);
+  }
+}
+
 // Blocked Bloom prefilter: k=2 bits in ONE u32 word (one 4 B read per
 // probe, one cache line touched) — ~94% of probe misses skip the
 // table-line read. bloom_mask = bit count - 1 (pow2; words = bits/32).
@@ -988,19 +1057,7 @@ __global__ void __launch_bounds__(BLOCK) k_join_build2(
   uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
-    int64_t key = keys[i];
-    uint64_t s = slot_of(key, cap);
-    for (;;) {
-      int64_t cur = slot_keys[s];
-      if (cur == key) break;
-      if (cur == QK_JOIN_EMPTY) {
-        int64_t prev = (int64_t)atomicCAS((unsigned long long *)&slot_keys[s],
-                                          (unsigned long long)QK_JOIN_EMPTY,
-                                          (unsigned long long)key);
-        if (prev == QK_JOIN_EMPTY || prev == key) break;
-      }
-      s = (s + 1) & (cap - 1);
-    }
+    uint64_t s = ht_find_or_insert(slot_keys, cap, keys[i]);
     int32_t me = (int32_t)(row_offset + i);
     int32_t old = atomicExch(&slot_head[s], me);
     chain_next[me] = old;
@@ -1012,8 +1069,8 @@ extern "C" int qk_join_build(void *stream, uint64_t n, const int64_t *keys,
                              int32_t *slot_head, int32_t *chain_next,
                              uint64_t cap) {
   if (!n) return 0;
-  if (cap & (cap - 1)) return qk_fail("qk_join_build.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  if (!qk_pow2(cap)) return qk_fail("qk_join_build.cap_pow2", hipErrorInvalidValue);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_join_build2, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, keys, row_offset, slot_keys,
                      slot_head, chain_next, cap);
@@ -1030,18 +1087,7 @@ __global__ void __launch_bounds__(BLOCK) k_join_probe(
   uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
-    int64_t key = keys[i];
-    uint64_t s = slot_of(key, cap);
-    int32_t head = -1;
-    for (;;) {
-      int64_t cur = slot_keys[s];
-      if (cur == key) {
-        head = slot_head[s];
-        break;
-      }
-      if (cur == QK_JOIN_EMPTY) break;
-      s = (s + 1) & (cap - 1);
-    }
+    int32_t head = probe_unique(slot_keys, slot_head, cap, keys[i], nullptr);
     if (mode == 1) {  // semi
       if (head >= 0) {
         uint64_t pos = atomicAdd((unsigned long long *)cursor, 1ULL);
@@ -1076,8 +1122,8 @@ extern "C" int qk_join_probe(void *stream, uint64_t n, const int64_t *keys,
                              uint32_t *out_probe, uint32_t *out_build,
                              uint64_t out_cap, uint64_t *cursor) {
   if (!n) return 0;
-  if (cap & (cap - 1)) return qk_fail("qk_join_probe.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  if (!qk_pow2(cap)) return qk_fail("qk_join_probe.cap_pow2", hipErrorInvalidValue);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_join_probe, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, keys, slot_keys, slot_head,
                      chain_next, cap, mode, out_probe, out_build, out_cap,
@@ -1105,18 +1151,7 @@ __global__ void __launch_bounds__(BLOCK) k_build_u8eq(
        i += stride) {
     if (flag[i] != flag_val) continue;
     int64_t key = keys[i];
-    uint64_t s = slot_of(key, cap);
-    for (;;) {
-      int64_t cur = slot_keys[s];
-      if (cur == key) break;
-      if (cur == QK_JOIN_EMPTY) {
-        int64_t prev = (int64_t)atomicCAS((unsigned long long *)&slot_keys[s],
-                                          (unsigned long long)QK_JOIN_EMPTY,
-                                          (unsigned long long)key);
-        if (prev == QK_JOIN_EMPTY || prev == key) break;
-      }
-      s = (s + 1) & (cap - 1);
-    }
+    uint64_t s = ht_find_or_insert(slot_keys, cap, key);
     slot_head[s] = (int32_t)i;
     if (bloom) bloom_set(bloom, bloom_mask, key);
   }
@@ -1127,29 +1162,13 @@ extern "C" int qk_build_u8eq(void *stream, uint64_t n, const int64_t *keys,
                              uint64_t cap, uint32_t *bloom,
                              uint64_t bloom_mask) {
   if (!n) return 0;
-  if (cap & (cap - 1)) return qk_fail("qk_build_u8eq.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  if (!qk_pow2(cap)) return qk_fail("qk_build_u8eq.cap_pow2", hipErrorInvalidValue);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_build_u8eq, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, keys, flag, flag_val, slot_keys,
                      slot_head, cap, bloom, bloom_mask);
   QK_TRY("qk_build_u8eq", hipGetLastError());
   return 0;
-}
-
-__device__ inline int32_t probe_unique(const int64_t *__restrict__ slot_keys,
-                                       const int32_t *__restrict__ slot_head,
-                                       uint64_t cap, int64_t key,
-                                       uint64_t *slot_out) {
-  uint64_t s = slot_of(key, cap);
-  for (;;) {
-    int64_t cur = slot_keys[s];
-    if (cur == key) {
-      if (slot_out) *slot_out = s;
-      return slot_head[s];
-    }
-    if (cur == QK_JOIN_EMPTY) return -1;
-    s = (s + 1) & (cap - 1);
-  }
 }
 
 // orders: insert o_orderkey[i] where o_orderdate[i] < date_lt AND
@@ -1164,18 +1183,7 @@ __device__ inline void q3_build_row(
   if (!pass) return;
   if (probe_unique(cust_keys, cust_head, cust_cap, ck, nullptr) < 0) return;
   int64_t key = __builtin_nontemporal_load(&o_orderkey[i]);
-  uint64_t s = slot_of(key, cap);
-  for (;;) {
-    int64_t cur = slot_keys[s];
-    if (cur == key) break;
-    if (cur == QK_JOIN_EMPTY) {
-      int64_t prev = (int64_t)atomicCAS((unsigned long long *)&slot_keys[s],
-                                        (unsigned long long)QK_JOIN_EMPTY,
-                                        (unsigned long long)key);
-      if (prev == QK_JOIN_EMPTY || prev == key) break;
-    }
-    s = (s + 1) & (cap - 1);
-  }
+  uint64_t s = ht_find_or_insert(slot_keys, cap, key);
   slot_head[s] = (int32_t)i;
   if (bloom) bloom_set(bloom, bloom_mask, key);
 }
@@ -1233,9 +1241,9 @@ extern "C" int qk_q3_build_orders(void *stream, uint64_t n,
                                   const uint32_t *cbloom,
                                   uint64_t cbloom_mask) {
   if (!n) return 0;
-  if ((cap & (cap - 1)) || (cust_cap & (cust_cap - 1)))
+  if (!qk_pow2(cap) || !qk_pow2(cust_cap))
     return qk_fail("qk_q3_build_orders.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_q3_build_orders, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, o_orderkey, o_custkey,
                      o_orderdate, date_lt, cust_keys, cust_head, cust_cap,
@@ -1264,16 +1272,7 @@ __global__ void __launch_bounds__(BLOCK) k_q3_count_orders(
     if (probe_unique(cust_keys, cust_head, cust_cap, ck, nullptr) >= 0)
       cnt++;
   }
-  __shared__ uint32_t lds[BLOCK / WAVE];
-  for (int off = WAVE / 2; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
-  int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  if (lane == 0) lds[wid] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t s = 0;
-    for (int w = 0; w < BLOCK / WAVE; w++) s += lds[w];
-    if (s) atomicAdd((unsigned long long *)count, (unsigned long long)s);
-  }
+  block_add_count(cnt, count);
 }
 extern "C" int qk_q3_count_orders(void *stream, uint64_t n,
                                   const int64_t *o_custkey,
@@ -1283,7 +1282,7 @@ extern "C" int qk_q3_count_orders(void *stream, uint64_t n,
                                   uint64_t *count_dev, const uint32_t *cbloom,
                                   uint64_t cbloom_mask) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_q3_count_orders, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, o_custkey, o_orderdate, date_lt,
                      cust_keys, cust_head, cust_cap, count_dev, cbloom,
@@ -1313,20 +1312,7 @@ __global__ void __launch_bounds__(BLOCK) k_q3_probe_agg(
     matches++;
     atomicAdd(&slot_sums[s], l_price[i] * (1.0 - l_disc[i]));
   }
-  if (match_count) {
-    __shared__ uint32_t lds[BLOCK / WAVE];
-    for (int off = WAVE / 2; off > 0; off >>= 1)
-      matches += __shfl_down(matches, off);
-    int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-    if (lane == 0) lds[wid] = matches;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint64_t t = 0;
-      for (int w = 0; w < BLOCK / WAVE; w++) t += lds[w];
-      if (t) atomicAdd((unsigned long long *)match_count,
-                       (unsigned long long)t);
-    }
-  }
+  if (match_count) block_add_count(matches, match_count);
 }
 // nt variant: non-temporal loads on the streamed lineitem columns keep
 // the hash table cache-resident (the streaming scan otherwise evicts it;
@@ -1337,24 +1323,67 @@ __device__ inline void q3_probe_row(
     const int32_t *__restrict__ slot_head, uint64_t cap,
     double *__restrict__ slot_sums, uint32_t &matches) {
   if (!pass) return;
-  uint64_t s = slot_of(key, cap);
-  int32_t head = -1;
-  for (;;) {
-    int64_t cur = slot_keys[s];
-    if (cur == key) { head = slot_head[s]; break; }
-    if (cur == QK_JOIN_EMPTY) break;
-    s = (s + 1) & (cap - 1);
-  }
-  if (head < 0) return;
+  uint64_t s;
+  if (probe_unique(slot_keys, slot_head, cap, key, &s) < 0) return;
   matches++;
   double price = __builtin_nontemporal_load(&l_price[i]);
   double disc = __builtin_nontemporal_load(&l_disc[i]);
   atomicAdd(&slot_sums[s], price * (1.0 - disc));
 }
 
+// The non-temporal probe at R rows per lane. Each lane takes R adjacent
+// rows with one vector nt load per streamed key column (R x 4 B of
+// shipdate, R x 8 B of orderkey), runs the R bloom tests and then up to R
+// independent table walks: the probes are random-load latency-bound at
+// full occupancy, so rows per lane = load chains in flight. The n % R
+// rows past the last full group go to thread 0 of block 0, row by row.
+template <int R>
+__device__ inline void q3_probe_nt_body(
+    uint64_t n, const int64_t *__restrict__ l_orderkey,
+    const int32_t *__restrict__ l_shipdate,
+    const double *__restrict__ l_price, const double *__restrict__ l_disc,
+    int32_t date_gt, const int64_t *__restrict__ slot_keys,
+    const int32_t *__restrict__ slot_head, uint64_t cap,
+    double *__restrict__ slot_sums, uint64_t *__restrict__ match_count,
+    const uint32_t *__restrict__ bloom, uint64_t bloom_mask) {
+  typedef int vRi __attribute__((ext_vector_type(R)));
+  typedef long long vRl __attribute__((ext_vector_type(R)));
+  uint32_t matches = 0;
+  uint64_t ngroups = n / R;
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       g < ngroups; g += stride) {
+    uint64_t i = R * g;
+    vRi sR = __builtin_nontemporal_load(
+        reinterpret_cast<const vRi *>(l_shipdate + i));
+    vRl kR = __builtin_nontemporal_load(
+        reinterpret_cast<const vRl *>(l_orderkey + i));
+    bool pass[R];
+#pragma unroll
+    for (int j = 0; j < R; j++) pass[j] = sR[j] > date_gt;
+    if (bloom) {
+#pragma unroll
+      for (int j = 0; j < R; j++)
+        if (pass[j]) pass[j] = bloom_test(bloom, bloom_mask, kR[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < R; j++)
+      q3_probe_row(kR[j], pass[j], i + j, l_price, l_disc, slot_keys,
+                   slot_head, cap, slot_sums, matches);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    for (uint64_t i = ngroups * R; i < n; i++)
+      if (l_shipdate[i] > date_gt) {
+        int64_t key = l_orderkey[i];
+        bool pass = !bloom || bloom_test(bloom, bloom_mask, key);
+        q3_probe_row(key, pass, i, l_price, l_disc, slot_keys, slot_head,
+                     cap, slot_sums, matches);
+      }
+  if (match_count) block_add_count(matches, match_count);
+}
+
 // 2 rows/thread: int2/long2 nt loads (8/16 B per lane, the coalescing
-// sweet spot) and two independent bloom/table lookups in flight per
-// thread (the probes are random-load latency-bound at full occupancy)
+// sweet spot) — the default probe
 __global__ void __launch_bounds__(BLOCK) k_q3_probe_agg_nt(
     uint64_t n, const int64_t *__restrict__ l_orderkey,
     const int32_t *__restrict__ l_shipdate,
@@ -1363,58 +1392,13 @@ __global__ void __launch_bounds__(BLOCK) k_q3_probe_agg_nt(
     const int32_t *__restrict__ slot_head, uint64_t cap,
     double *__restrict__ slot_sums, uint64_t *__restrict__ match_count,
     const uint32_t *__restrict__ bloom, uint64_t bloom_mask) {
-  uint32_t matches = 0;
-  uint64_t npairs = n / 2;
-  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       p < npairs; p += stride) {
-    uint64_t i = 2 * p;
-    typedef int v2i __attribute__((ext_vector_type(2)));
-    typedef long long v2l __attribute__((ext_vector_type(2)));
-    v2i s2 = __builtin_nontemporal_load(
-        reinterpret_cast<const v2i *>(l_shipdate + i));
-    v2l k2 = __builtin_nontemporal_load(
-        reinterpret_cast<const v2l *>(l_orderkey + i));
-    bool pass0 = s2.x > date_gt, pass1 = s2.y > date_gt;
-    if (bloom) {
-      if (pass0) pass0 = bloom_test(bloom, bloom_mask, k2.x);
-      if (pass1) pass1 = bloom_test(bloom, bloom_mask, k2.y);
-    }
-    q3_probe_row(k2.x, pass0, i, l_price, l_disc, slot_keys, slot_head,
-                 cap, slot_sums, matches);
-    q3_probe_row(k2.y, pass1, i + 1, l_price, l_disc, slot_keys, slot_head,
-                 cap, slot_sums, matches);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) {
-    uint64_t i = n - 1;
-    if (l_shipdate[i] > date_gt) {
-      int64_t key = l_orderkey[i];
-      bool pass = !bloom || bloom_test(bloom, bloom_mask, key);
-      q3_probe_row(key, pass, i, l_price, l_disc, slot_keys, slot_head,
-                   cap, slot_sums, matches);
-    }
-  }
-  if (match_count) {
-    __shared__ uint32_t lds[BLOCK / WAVE];
-    for (int off = WAVE / 2; off > 0; off >>= 1)
-      matches += __shfl_down(matches, off);
-    int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-    if (lane == 0) lds[wid] = matches;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint64_t t = 0;
-      for (int w = 0; w < BLOCK / WAVE; w++) t += lds[w];
-      if (t) atomicAdd((unsigned long long *)match_count,
-                       (unsigned long long)t);
-    }
-  }
+  q3_probe_nt_body<2>(n, l_orderkey, l_shipdate, l_price, l_disc, date_gt,
+                      slot_keys, slot_head, cap, slot_sums, match_count,
+                      bloom, bloom_mask);
 }
-
-// 4 rows/thread experiment: the probe is random-load latency-bound at
-// full occupancy (r01 stall anatomy), so the remaining lever is MORE
-// independent load chains per lane — 4 bloom tests + up to 4 table
-// walks in flight instead of 2. A/B'd against the 2-row kernel on
-// MI355X; see profiles/r02 notes for the verdict.
+// 4 rows/thread experiment: 4 bloom tests + up to 4 table walks in flight
+// instead of 2. A/B'd against the 2-row kernel on MI355X; see profiles/r02
+// notes for the verdict.
 __global__ void __launch_bounds__(BLOCK) k_q3_probe_agg_nt4(
     uint64_t n, const int64_t *__restrict__ l_orderkey,
     const int32_t *__restrict__ l_shipdate,
@@ -1423,53 +1407,9 @@ __global__ void __launch_bounds__(BLOCK) k_q3_probe_agg_nt4(
     const int32_t *__restrict__ slot_head, uint64_t cap,
     double *__restrict__ slot_sums, uint64_t *__restrict__ match_count,
     const uint32_t *__restrict__ bloom, uint64_t bloom_mask) {
-  uint32_t matches = 0;
-  uint64_t nquads = n / 4;
-  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       q < nquads; q += stride) {
-    uint64_t i = 4 * q;
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    typedef long long v4l __attribute__((ext_vector_type(4)));
-    v4i s4 = __builtin_nontemporal_load(
-        reinterpret_cast<const v4i *>(l_shipdate + i));
-    v4l k4 = __builtin_nontemporal_load(
-        reinterpret_cast<const v4l *>(l_orderkey + i));
-    bool pass[4] = {s4.x > date_gt, s4.y > date_gt, s4.z > date_gt,
-                    s4.w > date_gt};
-    int64_t keys[4] = {k4.x, k4.y, k4.z, k4.w};
-    if (bloom) {
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (pass[j]) pass[j] = bloom_test(bloom, bloom_mask, keys[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-      q3_probe_row(keys[j], pass[j], i + j, l_price, l_disc, slot_keys,
-                   slot_head, cap, slot_sums, matches);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0)
-    for (uint64_t i = nquads * 4; i < n; i++)
-      if (l_shipdate[i] > date_gt) {
-        int64_t key = l_orderkey[i];
-        bool pass = !bloom || bloom_test(bloom, bloom_mask, key);
-        q3_probe_row(key, pass, i, l_price, l_disc, slot_keys, slot_head,
-                     cap, slot_sums, matches);
-      }
-  if (match_count) {
-    __shared__ uint32_t lds[BLOCK / WAVE];
-    for (int off = WAVE / 2; off > 0; off >>= 1)
-      matches += __shfl_down(matches, off);
-    int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-    if (lane == 0) lds[wid] = matches;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint64_t t = 0;
-      for (int w = 0; w < BLOCK / WAVE; w++) t += lds[w];
-      if (t) atomicAdd((unsigned long long *)match_count,
-                       (unsigned long long)t);
-    }
-  }
+  q3_probe_nt_body<4>(n, l_orderkey, l_shipdate, l_price, l_disc, date_gt,
+                      slot_keys, slot_head, cap, slot_sums, match_count,
+                      bloom, bloom_mask);
 }
 extern "C" int qk_q3_probe_agg_nt4(void *stream, uint64_t n,
                                    const int64_t *l_orderkey,
@@ -1482,10 +1422,9 @@ extern "C" int qk_q3_probe_agg_nt4(void *stream, uint64_t n,
                                    const uint32_t *bloom,
                                    uint64_t bloom_mask) {
   if (!n) return 0;
-  if (cap & (cap - 1))
+  if (!qk_pow2(cap))
     return qk_fail("qk_q3_probe_agg_nt4.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks =
-      (uint32_t)qk_min_u64(MAX_BLOCKS, (n / 4 + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n / 4);
   hipLaunchKernelGGL(k_q3_probe_agg_nt4, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, l_orderkey, l_shipdate,
                      l_price, l_disc, date_gt, slot_keys, slot_head, cap,
@@ -1502,9 +1441,9 @@ extern "C" int qk_q3_probe_agg(void *stream, uint64_t n,
                                const int32_t *slot_head, uint64_t cap,
                                double *slot_sums, uint64_t *match_count) {
   if (!n) return 0;
-  if (cap & (cap - 1))
+  if (!qk_pow2(cap))
     return qk_fail("qk_q3_probe_agg.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_q3_probe_agg, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, l_orderkey, l_shipdate, l_price,
                      l_disc, date_gt, slot_keys, slot_head, cap, slot_sums,
@@ -1522,9 +1461,9 @@ extern "C" int qk_q3_probe_agg_nt(void *stream, uint64_t n,
                                   const uint32_t *bloom,
                                   uint64_t bloom_mask) {
   if (!n) return 0;
-  if (cap & (cap - 1))
+  if (!qk_pow2(cap))
     return qk_fail("qk_q3_probe_agg_nt.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_q3_probe_agg_nt, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, l_orderkey, l_shipdate, l_price,
                      l_disc, date_gt, slot_keys, slot_head, cap, slot_sums,
@@ -1546,16 +1485,8 @@ __global__ void __launch_bounds__(BLOCK) k_extract_count(
   uint32_t cnt = 0;
   for (uint64_t st = lo + threadIdx.x; st < hi; st += BLOCK)
     cnt += (slot_keys[st] != QK_JOIN_EMPTY && slot_sums[st] != 0.0) ? 1u : 0u;
-  __shared__ uint32_t lds[BLOCK / WAVE];
-  for (int off = WAVE / 2; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
-  int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  if (lane == 0) lds[wid] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t t = 0;
-    for (int w = 0; w < BLOCK / WAVE; w++) t += lds[w];
-    block_counts[blockIdx.x] = t;
-  }
+  uint64_t t = block_sum(cnt);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = t;
 }
 
 __global__ void __launch_bounds__(BLOCK) k_extract_scatter(
@@ -1642,18 +1573,7 @@ __global__ void __launch_bounds__(BLOCK) k_build_keyval_i32(
         !((accept_mask >> (v & 31)) & 1u && v >= 0 && v < 32))
       continue;
     int64_t key = keys[i];
-    uint64_t s = slot_of(key, cap);
-    for (;;) {
-      int64_t cur = slot_keys[s];
-      if (cur == key) break;
-      if (cur == QK_JOIN_EMPTY) {
-        int64_t prev = (int64_t)atomicCAS((unsigned long long *)&slot_keys[s],
-                                          (unsigned long long)QK_JOIN_EMPTY,
-                                          (unsigned long long)key);
-        if (prev == QK_JOIN_EMPTY || prev == key) break;
-      }
-      s = (s + 1) & (cap - 1);
-    }
+    uint64_t s = ht_find_or_insert(slot_keys, cap, key);
     slot_val[s] = v;
     if (bloom) bloom_set(bloom, bloom_mask, key);
   }
@@ -1664,9 +1584,9 @@ extern "C" int qk_build_keyval_i32(void *stream, uint64_t n,
                                    int32_t *slot_val, uint64_t cap,
                                    uint32_t *bloom, uint64_t bloom_mask) {
   if (!n) return 0;
-  if (cap & (cap - 1))
+  if (!qk_pow2(cap))
     return qk_fail("qk_build_keyval_i32.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_build_keyval_i32, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, keys, vals, accept_mask,
                      slot_keys, slot_val, cap, bloom, bloom_mask);
@@ -1700,33 +1620,11 @@ __global__ void __launch_bounds__(BLOCK) k_q5_build_orders(
     cnt++;
     if (!slot_keys) continue;
     int64_t key = o_orderkey[i];
-    uint64_t s = slot_of(key, cap);
-    for (;;) {
-      int64_t cur = slot_keys[s];
-      if (cur == key) break;
-      if (cur == QK_JOIN_EMPTY) {
-        int64_t prev = (int64_t)atomicCAS((unsigned long long *)&slot_keys[s],
-                                          (unsigned long long)QK_JOIN_EMPTY,
-                                          (unsigned long long)key);
-        if (prev == QK_JOIN_EMPTY || prev == key) break;
-      }
-      s = (s + 1) & (cap - 1);
-    }
+    uint64_t s = ht_find_or_insert(slot_keys, cap, key);
     slot_val[s] = nat;
     if (bloom) bloom_set(bloom, bloom_mask, key);
   }
-  if (count) {
-    __shared__ uint32_t lds[BLOCK / WAVE];
-    for (int off = WAVE / 2; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
-    int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-    if (lane == 0) lds[wid] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint64_t t = 0;
-      for (int w = 0; w < BLOCK / WAVE; w++) t += lds[w];
-      if (t) atomicAdd((unsigned long long *)count, (unsigned long long)t);
-    }
-  }
+  if (count) block_add_count(cnt, count);
 }
 extern "C" int qk_q5_build_orders(void *stream, uint64_t n,
                                   const int64_t *o_orderkey,
@@ -1740,9 +1638,9 @@ extern "C" int qk_q5_build_orders(void *stream, uint64_t n,
                                   const uint32_t *cbloom,
                                   uint64_t cbloom_mask) {
   if (!n) return 0;
-  if ((cust_cap & (cust_cap - 1)) || (slot_keys && (cap & (cap - 1))))
+  if (!qk_pow2(cust_cap) || (slot_keys && !qk_pow2(cap)))
     return qk_fail("qk_q5_build_orders.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_q5_build_orders, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, o_orderkey, o_custkey,
                      o_orderdate, date_lo, date_hi, cust_keys, cust_val,
@@ -1862,9 +1760,9 @@ extern "C" int qk_q5_probe_agg(void *stream, uint64_t n,
                                const int32_t *supp_val, uint64_t supp_cap,
                                double *out25, uint64_t *match_count) {
   if (!n) return 0;
-  if ((ord_cap & (ord_cap - 1)) || (supp_cap & (supp_cap - 1)))
+  if (!qk_pow2(ord_cap) || !qk_pow2(supp_cap))
     return qk_fail("qk_q5_probe_agg.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_q5_probe_agg, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, l_orderkey, l_suppkey, l_price,
                      l_disc, ord_keys, ord_val, ord_cap, supp_keys, supp_val,
@@ -1884,9 +1782,9 @@ extern "C" int qk_q5_probe_agg_nt(void *stream, uint64_t n,
                                   const uint32_t *bloom,
                                   uint64_t bloom_mask) {
   if (!n) return 0;
-  if ((ord_cap & (ord_cap - 1)) || (supp_cap & (supp_cap - 1)))
+  if (!qk_pow2(ord_cap) || !qk_pow2(supp_cap))
     return qk_fail("qk_q5_probe_agg_nt.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_q5_probe_agg_nt, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, l_orderkey, l_suppkey, l_price,
                      l_disc, ord_keys, ord_val, ord_cap, supp_keys, supp_val,
@@ -1913,23 +1811,13 @@ __global__ void __launch_bounds__(BLOCK) k_bloom_count(
     cnt += bloom_test(bloom, bloom_mask, k2.x) ? 1u : 0u;
     cnt += bloom_test(bloom, bloom_mask, k2.y) ? 1u : 0u;
   }
-  __shared__ uint32_t lds[BLOCK / WAVE];
-  for (int off = WAVE / 2; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
-  int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  if (lane == 0) lds[wid] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t t = 0;
-    for (int w = 0; w < BLOCK / WAVE; w++) t += lds[w];
-    if (t) atomicAdd((unsigned long long *)out, (unsigned long long)t);
-  }
+  block_add_count(cnt, out);
 }
 extern "C" int qk_bloom_count(void *stream, uint64_t n, const int64_t *keys,
                               const uint32_t *bloom, uint64_t bloom_mask,
                               uint64_t *out) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n / 2 + BLOCK - 1) / BLOCK);
-  if (!blocks) blocks = 1;
+  uint32_t blocks = qk_grid(n / 2);
   hipLaunchKernelGGL(k_bloom_count, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, keys, bloom, bloom_mask, out);
   QK_TRY("qk_bloom_count", hipGetLastError());
@@ -1975,7 +1863,7 @@ extern "C" int qk_gen_aux(void *stream, uint64_t n, uint64_t row_offset,
                           uint64_t seed, uint64_t salt, int mode, int64_t a,
                           int64_t b, uint8_t *out_u8, double *out_f64) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_gen_aux, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, row_offset, seed, salt, mode,
                      a, b, out_u8, out_f64);
@@ -1987,7 +1875,7 @@ extern "C" int qk_gen_supplier(void *stream, uint64_t n, uint64_t row_offset,
                                uint64_t seed, int64_t *s_suppkey,
                                int32_t *s_nationkey) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_gen_supplier, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, row_offset, seed, s_suppkey,
                      s_nationkey);
@@ -2033,6 +1921,9 @@ __global__ void __launch_bounds__(BLOCK) k_groupby_sum(
   uint32_t my_inserts = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
+    // ht_find_or_insert over strided records, kept written out: it keeps
+    // the record pointer and counts its own claims, and routing it through
+    // the helper (stride + claimed flag) measured slower on Q18
     int64_t key = keys[i];
     uint64_t s = slot_of(key, cap);
     int64_t *rec;
@@ -2066,20 +1957,7 @@ __global__ void __launch_bounds__(BLOCK) k_groupby_sum(
         atomicAdd(&vslot[c], v);
     }
   }
-  if (n_inserted) {
-    __shared__ uint32_t lds[BLOCK / WAVE];
-    for (int off = WAVE / 2; off > 0; off >>= 1)
-      my_inserts += __shfl_down(my_inserts, off);
-    int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-    if (lane == 0) lds[wid] = my_inserts;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint64_t t = 0;
-      for (int w = 0; w < BLOCK / WAVE; w++) t += lds[w];
-      if (t) atomicAdd((unsigned long long *)n_inserted,
-                       (unsigned long long)t);
-    }
-  }
+  if (n_inserted) block_add_count(my_inserts, n_inserted);
 }
 __global__ void k_groupby_init(uint64_t cap, int rstride, int nvals,
                                const double *__restrict__ inits,
@@ -2097,7 +1975,7 @@ extern "C" int qk_groupby_init(void *stream, int64_t *table, uint64_t cap,
                                int rstride, int nvals,
                                const double *inits_dev) {
   if (!cap) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (cap + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(cap);
   hipLaunchKernelGGL(k_groupby_init, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, cap, rstride, nvals, inits_dev,
                      table);
@@ -2110,11 +1988,11 @@ extern "C" int qk_groupby_i64_sum(void *stream, uint64_t n, const int64_t *keys,
                                   int rstride, int64_t *table, uint64_t cap,
                                   uint64_t *n_inserted) {
   if (!n) return 0;
-  if (cap & (cap - 1))
+  if (!qk_pow2(cap))
     return qk_fail("qk_groupby_i64_sum.cap_pow2", hipErrorInvalidValue);
-  if (rstride < 1 + nvals || (rstride & (rstride - 1)))
+  if (rstride < 1 + nvals || !qk_pow2((uint64_t)rstride))
     return qk_fail("qk_groupby_i64_sum.rstride", hipErrorInvalidValue);
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_groupby_sum, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, keys,
                      (const double *const *)vals_dev, agg_ops_dev, nvals,
@@ -2131,7 +2009,7 @@ __global__ void k_fill_f64(double *dst, double v, uint64_t n) {
 }
 extern "C" int qk_fill_f64(void *stream, double *dst, double v, uint64_t n) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_fill_f64, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, dst, v, n);
   QK_TRY("qk_fill_f64", hipGetLastError());
@@ -2175,7 +2053,7 @@ extern "C" int qk_groupby_extract(void *stream, const int64_t *table,
                                   int rstride, int nvals, uint64_t cap,
                                   int64_t *out_keys, double *out_sums,
                                   uint64_t out_cap, uint64_t *cursor) {
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (cap + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(cap);
   hipLaunchKernelGGL(k_groupby_extract, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, table, rstride, nvals, cap,
                      out_keys, out_sums, out_cap, cursor);
@@ -2222,7 +2100,7 @@ extern "C" int qk_groupby_extract_gt(void *stream, const int64_t *table,
                                      int col, double threshold,
                                      int64_t *out_keys, double *out_sums,
                                      uint64_t out_cap, uint64_t *cursor) {
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (cap + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(cap);
   hipLaunchKernelGGL(k_groupby_extract_gt, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, table, rstride, nvals, cap, col,
                      threshold, out_keys, out_sums, out_cap, cursor);
@@ -2382,7 +2260,7 @@ __global__ void k_iota_u32(uint64_t n, uint32_t *__restrict__ out) {
 extern "C" int qk_map_f64_u64(void *stream, uint64_t n, const double *in,
                               uint64_t *out) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_map_f64_u64, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, in, out);
   QK_TRY("qk_map_f64_u64", hipGetLastError());
@@ -2391,7 +2269,7 @@ extern "C" int qk_map_f64_u64(void *stream, uint64_t n, const double *in,
 extern "C" int qk_map_i64_u64(void *stream, uint64_t n, const int64_t *in,
                               uint64_t *out) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_map_i64_u64, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, in, out);
   QK_TRY("qk_map_i64_u64", hipGetLastError());
@@ -2399,7 +2277,7 @@ extern "C" int qk_map_i64_u64(void *stream, uint64_t n, const int64_t *in,
 }
 extern "C" int qk_bnot_u64(void *stream, uint64_t n, uint64_t *x) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_bnot_u64, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, x);
   QK_TRY("qk_bnot_u64", hipGetLastError());
@@ -2407,7 +2285,7 @@ extern "C" int qk_bnot_u64(void *stream, uint64_t n, uint64_t *x) {
 }
 extern "C" int qk_iota_u32(void *stream, uint64_t n, uint32_t *out) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_iota_u32, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, out);
   QK_TRY("qk_iota_u32", hipGetLastError());
@@ -2437,8 +2315,7 @@ extern "C" int qk_sort_pairs_u64(void *stream, uint64_t n, uint64_t *keys,
   if (npasses < 0) {
     QK_TRY("qk_sort_pairs_u64",
            hipMemsetAsync(dmax, 0, 8, (hipStream_t)stream));
-    uint32_t b2 = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(k_reduce_max_u64, dim3(b2), dim3(BLOCK), 0,
+    hipLaunchKernelGGL(k_reduce_max_u64, dim3(qk_grid(n)), dim3(BLOCK), 0,
                        (hipStream_t)stream, n, keys, dmax);
     unsigned long long hmax = 0;
     QK_TRY("qk_sort_pairs_u64",
@@ -2728,9 +2605,9 @@ extern "C" int qk_str_dict_encode(void *stream, uint64_t n,
                                   uint8_t *arena, uint64_t *arena_cursor,
                                   uint32_t *counter, uint32_t *out_codes) {
   if (!n) return 0;
-  if (cap & (cap - 1))
+  if (!qk_pow2(cap))
     return qk_fail("qk_str_dict_encode.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_str_dict_encode, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, offsets, bytes, slot_hash,
                      slot_code, cap, code_off, code_len, arena,
@@ -2768,10 +2645,9 @@ extern "C" int qk_str_dict_rehash(void *stream, uint32_t ncodes,
                                   const uint8_t *arena, uint64_t *slot_hash,
                                   int32_t *slot_code, uint64_t cap) {
   if (!ncodes) return 0;
-  if (cap & (cap - 1))
+  if (!qk_pow2(cap))
     return qk_fail("qk_str_dict_rehash.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks =
-      (uint32_t)qk_min_u64(MAX_BLOCKS, (ncodes + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(ncodes);
   hipLaunchKernelGGL(k_str_dict_rehash, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, ncodes, code_off, code_len, arena,
                      slot_hash, slot_code, cap);
@@ -3071,7 +2947,7 @@ __global__ void __launch_bounds__(BLOCK) k_i64_combine(
 extern "C" int qk_i64_combine(void *stream, uint64_t n, const int64_t *x,
                               const int64_t *y, int64_t scale, int64_t *out) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_i64_combine, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, x, y, scale, out);
   QK_TRY("qk_i64_combine", hipGetLastError());
@@ -3090,7 +2966,7 @@ __global__ void __launch_bounds__(BLOCK) k_i64_shr(
 extern "C" int qk_i64_shr(void *stream, uint64_t n, const int64_t *x,
                           int shift, int64_t *out) {
   if (!n) return 0;
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_i64_shr, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, x, shift, out);
   QK_TRY("qk_i64_shr", hipGetLastError());
@@ -3768,7 +3644,7 @@ extern "C" int qk_range_part_ids(void *stream, uint64_t n,
   if (!n) return 0;
   if (per_range <= 0 || !nparts)
     return qk_fail("qk_range_part_ids", hipErrorInvalidValue);
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_range_part_ids, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, keys, per_range, nparts, out);
   QK_TRY("qk_range_part_ids", hipGetLastError());
@@ -3790,16 +3666,8 @@ __global__ void __launch_bounds__(BLOCK) k_csv_nl_count(
   uint32_t cnt = 0;
   for (uint64_t r = lo + threadIdx.x; r < hi; r += BLOCK)
     cnt += b[r] == '\n' ? 1u : 0u;
-  __shared__ uint32_t lds[BLOCK / WAVE];
-  for (int off = WAVE / 2; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
-  int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  if (lane == 0) lds[wid] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t s = 0;
-    for (int w = 0; w < BLOCK / WAVE; w++) s += lds[w];
-    block_counts[blockIdx.x] = s;
-  }
+  uint64_t s = block_sum(cnt);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = s;
 }
 
 __global__ void __launch_bounds__(BLOCK) k_csv_nl_scatter(
@@ -3883,7 +3751,7 @@ __global__ void __launch_bounds__(BLOCK) k_csv_quote_count_w(
   uint32_t cnt = 0;
   for (uint64_t r = lo + lane; r < hi; r += WAVE)
     cnt += b[r] == quote ? 1u : 0u;
-  for (int off = WAVE / 2; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
+  cnt = wave_sum(cnt);
   if (lane == 0) counts[u] = cnt;
 }
 __global__ void __launch_bounds__(BLOCK) k_csv_nl_count_qw(
@@ -3906,7 +3774,7 @@ __global__ void __launch_bounds__(BLOCK) k_csv_nl_count_qw(
     cnt += valid ? 1u : 0u;
     in_q ^= (uint32_t)(__popcll(qmask) & 1u);
   }
-  for (int off = WAVE / 2; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
+  cnt = wave_sum(cnt);
   if (lane == 0) unit_counts[u] = cnt;
 }
 __global__ void __launch_bounds__(BLOCK) k_csv_nl_scatter_qw(
@@ -4129,8 +3997,7 @@ extern "C" int qk_csv_parse(void *stream, uint64_t nrows,
                             const uint8_t *dict_lens, const int *ncands,
                             uint64_t *err_row) {
   if (!nrows) return 0;
-  uint32_t blocks =
-      (uint32_t)qk_min_u64(MAX_BLOCKS, (nrows + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(nrows);
   hipLaunchKernelGGL(k_csv_parse, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, nrows, bytes, data_start, nl_pos,
                      sep, quote, ncols, coltypes, out_ptrs, dict_cands,
@@ -4229,7 +4096,7 @@ extern "C" int qk_partition_hist(void *stream, uint64_t n, const int64_t *keys,
   if (!n) return 0;
   if (!nparts)  // key % 0 on the device would index LDS with garbage
     return qk_fail("qk_partition_hist.nparts", hipErrorInvalidValue);
-  uint32_t blocks = (uint32_t)qk_min_u64(MAX_BLOCKS, (n + BLOCK - 1) / BLOCK);
+  uint32_t blocks = qk_grid(n);
   hipLaunchKernelGGL(k_partition_hist, dim3(blocks), dim3(BLOCK),
                      nparts * sizeof(uint32_t), (hipStream_t)stream, n, keys,
                      nparts, hist);

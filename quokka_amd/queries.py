@@ -14,7 +14,8 @@ import ctypes
 import numpy as np
 
 from . import ops
-from .shim import DevBuffer, DevColumn, c_u64, c_vp, call
+from .shim import (DevBuffer, DevColumn, JOIN_EMPTY, c_i64, c_u64, c_vp,
+                   call)
 
 Q1_CUTOFF = 10471      # date '1998-12-01' - interval '90' day = 1998-09-02
 Q3_DATE = 9204         # 1995-03-15
@@ -187,77 +188,116 @@ def q3(li_cols, ord_cols, cust_cols, stream=None, limit=10):
     return full, top10
 
 
+def _table_lf():
+    import os
+    return int(os.environ.get("QK_TABLE_LF", "4"))
+
+
+class _KeyTable:
+    """One open-addressing device table of the fused paths: i64 slot keys,
+    one i32 per slot (`val`: a build row or a value) and an optional Bloom
+    prefilter. `args` / `bloom_args` are the (keys, val, cap) and
+    (bloom, bloom_mask) argument runs every kernel takes for a table."""
+
+    def __init__(self, cap, bloom_bits=0, val_fill=None):
+        self.cap, self.bloom_bits, self.val_fill = cap, bloom_bits, val_fill
+        self.keys = DevColumn(np.int64, cap)
+        self.val = DevColumn(np.int32, cap)
+        self.bloom = DevColumn(np.uint32, bloom_bits // 32) \
+            if bloom_bits else None
+        self.args = (self.keys.ptr, self.val.ptr, c_u64(cap))
+        self.bloom_args = (self.bloom.ptr if self.bloom else None,
+                           c_u64(max(bloom_bits, 1) - 1))
+
+    def clear(self, sh):
+        """Back to empty: every key slot free, the Bloom bits zero, and
+        every val = val_fill bytes (None: vals are read only under a key
+        hit, so stale ones are never seen)."""
+        call("qk_fill_i64", sh, self.keys.ptr, c_i64(int(JOIN_EMPTY)),
+             c_u64(self.cap))
+        if self.val_fill is not None:
+            call("qk_dmemset", self.val.ptr, self.val_fill,
+                 c_u64(self.cap * 4))
+        if self.bloom:
+            call("qk_dmemset", self.bloom.ptr, 0, c_u64(self.bloom_bits // 8))
+
+    def free(self):
+        for c in (self.keys, self.val, self.bloom):
+            if c is not None:
+                c.free()
+
+
 class Q3Fused:
     """Fused Q3 state: customer+orders build tables on device. Split from
     the one-shot q3_fused() so bench can build once and probe per step."""
 
     def __init__(self, ord_cols, cust_cols, stream=None):
-        from . import shim, ops
-        from .shim import DevColumn, c_u64, c_i64
         self.stream = stream
-        sh = stream.handle if stream else None
-        ncust = cust_cols["c_custkey"].n
-        nord = ord_cols["o_orderkey"].n
+        self._ord_cols = ord_cols
+        self._cust_cols = cust_cols
         # size the customer table by the BUILDING survivor count, not the
         # full table (table bytes drive probe traffic — profiles/r01_q3)
         nbuild_cust = self._count_u8eq(cust_cols["c_mktsegment"],
                                        MKT_BUILDING, stream)
-        self.cust_cap = ops._pow2_at_least(max(16, 2 * nbuild_cust))
-        self.cust_keys = DevColumn(np.int64, self.cust_cap)
-        self.cust_head = DevColumn(np.int32, self.cust_cap)
-        self.cbloom_bits = ops._pow2_at_least(max(1 << 16, 8 * nbuild_cust))
-        self.cbloom = DevColumn(np.uint32, self.cbloom_bits // 32)
-        call("qk_dmemset", self.cbloom.ptr, 0, c_u64(self.cbloom_bits // 8))
-        call("qk_fill_i64", sh, self.cust_keys.ptr,
-             c_i64(int(shim.JOIN_EMPTY)), c_u64(self.cust_cap))
-        call("qk_dmemset", self.cust_head.ptr, 0xFF, c_u64(self.cust_cap * 4))
-        call("qk_build_u8eq", sh, c_u64(ncust), cust_cols["c_custkey"].ptr,
-             cust_cols["c_mktsegment"].ptr, ctypes.c_uint8(MKT_BUILDING),
-             self.cust_keys.ptr, self.cust_head.ptr, c_u64(self.cust_cap),
-             self.cbloom.ptr, c_u64(self.cbloom_bits - 1))
-        # tight orders-table sizing: count the fused-predicate survivors
-        # first so probes stay cache-resident (DESIGN.md §Q3)
+        self.cust = _KeyTable(
+            ops._pow2_at_least(max(16, 2 * nbuild_cust)),
+            ops._pow2_at_least(max(1 << 16, 8 * nbuild_cust)), val_fill=0xFF)
+        self.cust_cap = self.cust.cap
+        self.ord = None
+        self._build()
+
+    def _alloc_orders(self, sh):
+        """Tight orders-table sizing: count the fused-predicate survivors
+        (needs the built customer table) so probes stay cache-resident
+        (DESIGN.md §Q3). Bloom prefilter: ~8 bits/build key, k=2 (skips the
+        table-line read for ~95% of probe misses)."""
+        oc = self._ord_cols
         cnt = ops._count_buf()
-        call("qk_q3_count_orders", sh, c_u64(nord),
-             ord_cols["o_custkey"].ptr, ord_cols["o_orderdate"].ptr,
-             ctypes.c_int32(Q3_DATE), self.cust_keys.ptr,
-             self.cust_head.ptr, c_u64(self.cust_cap), cnt.ptr,
-             self.cbloom.ptr, c_u64(self.cbloom_bits - 1))
-        if stream:
-            stream.sync()
+        call("qk_q3_count_orders", sh, c_u64(oc["o_orderkey"].n),
+             oc["o_custkey"].ptr, oc["o_orderdate"].ptr,
+             ctypes.c_int32(Q3_DATE), *self.cust.args, cnt.ptr,
+             *self.cust.bloom_args)
+        if self.stream:
+            self.stream.sync()
         self.n_build = ops._read_u64(cnt)
         cnt.free()
-        import os
-        lf = int(os.environ.get("QK_TABLE_LF", "4"))
-        self.ord_cap = ops._pow2_at_least(max(16, lf * self.n_build))
-        self.ord_keys = DevColumn(np.int64, self.ord_cap)
-        self.ord_head = DevColumn(np.int32, self.ord_cap)
+        self.ord = _KeyTable(
+            ops._pow2_at_least(max(16, _table_lf() * self.n_build)),
+            ops._pow2_at_least(max(1 << 16, 8 * self.n_build)), val_fill=0xFF)
+        self.ord_cap, self.ord_keys = self.ord.cap, self.ord.keys
+        self.ord_head, self.bloom = self.ord.val, self.ord.bloom
+        self.bloom_bits = self.ord.bloom_bits
         self.ord_sums = DevColumn(np.float64, self.ord_cap)
-        # Bloom prefilter: ~8 bits/build key, k=2 (skips the table-line
-        # read for ~95% of probe misses)
-        self.bloom_bits = ops._pow2_at_least(max(1 << 16, 8 * self.n_build))
-        self.bloom = DevColumn(np.uint32, self.bloom_bits // 32)
-        call("qk_dmemset", self.bloom.ptr, 0, c_u64(self.bloom_bits // 8))
-        call("qk_fill_i64", sh, self.ord_keys.ptr,
-             c_i64(int(shim.JOIN_EMPTY)), c_u64(self.ord_cap))
-        call("qk_dmemset", self.ord_head.ptr, 0xFF, c_u64(self.ord_cap * 4))
-        call("qk_dmemset", self.ord_sums.ptr, 0, c_u64(self.ord_cap * 8))
-        call("qk_q3_build_orders", sh, c_u64(nord),
-             ord_cols["o_orderkey"].ptr, ord_cols["o_custkey"].ptr,
-             ord_cols["o_orderdate"].ptr, ctypes.c_int32(Q3_DATE),
-             self.cust_keys.ptr, self.cust_head.ptr, c_u64(self.cust_cap),
-             self.ord_keys.ptr, self.ord_head.ptr, c_u64(self.ord_cap),
-             self.bloom.ptr, c_u64(self.bloom_bits - 1),
-             self.cbloom.ptr, c_u64(self.cbloom_bits - 1))
-        self._ord_cols = ord_cols
-        self._cust_cols = cust_cols
+        self.ord.clear(sh)
+        self.reset_sums()
+
+    def _build(self):
+        """Clear the tables and run both build passes from the resident
+        base tables; the first call also sizes and allocates the orders
+        table, between the two passes."""
+        sh = self.stream.handle if self.stream else None
+        cc, oc = self._cust_cols, self._ord_cols
+        self.cust.clear(sh)
+        if self.ord:
+            self.ord.clear(sh)
+            self.reset_sums()
+        call("qk_build_u8eq", sh, c_u64(cc["c_custkey"].n),
+             cc["c_custkey"].ptr, cc["c_mktsegment"].ptr,
+             ctypes.c_uint8(MKT_BUILDING), *self.cust.args,
+             *self.cust.bloom_args)
+        if self.ord is None:
+            self._alloc_orders(sh)
+        call("qk_q3_build_orders", sh, c_u64(oc["o_orderkey"].n),
+             oc["o_orderkey"].ptr, oc["o_custkey"].ptr,
+             oc["o_orderdate"].ptr, ctypes.c_int32(Q3_DATE),
+             *self.cust.args, *self.ord.args, *self.ord.bloom_args,
+             *self.cust.bloom_args)
 
     @staticmethod
     def _count_u8eq(col, value, stream):
         """Count col == value with the filter-count kernel pair (no
         scatter pass; temp index buffer avoided by passing the count-only
         path through qk_filter_u8 on a scratch the size of the column)."""
-        from . import ops
         idx, n = ops.filter_col(col, ops.EQ, value, stream)
         idx.free()
         return n
@@ -268,66 +308,28 @@ class Q3Fused:
     def rebuild(self):
         """Re-run both build passes from the resident base tables (per-step
         full-query semantics in bench)."""
-        from . import shim
-        from .shim import c_u64, c_i64
-        sh = self.stream.handle if self.stream else None
-        call("qk_fill_i64", sh, self.cust_keys.ptr,
-             c_i64(int(shim.JOIN_EMPTY)), c_u64(self.cust_cap))
-        call("qk_dmemset", self.cust_head.ptr, 0xFF, c_u64(self.cust_cap * 4))
-        call("qk_fill_i64", sh, self.ord_keys.ptr,
-             c_i64(int(shim.JOIN_EMPTY)), c_u64(self.ord_cap))
-        call("qk_dmemset", self.ord_head.ptr, 0xFF, c_u64(self.ord_cap * 4))
-        call("qk_dmemset", self.ord_sums.ptr, 0, c_u64(self.ord_cap * 8))
-        call("qk_dmemset", self.bloom.ptr, 0, c_u64(self.bloom_bits // 8))
-        call("qk_dmemset", self.cbloom.ptr, 0, c_u64(self.cbloom_bits // 8))
-        call("qk_build_u8eq", sh, c_u64(self._cust_cols["c_custkey"].n),
-             self._cust_cols["c_custkey"].ptr,
-             self._cust_cols["c_mktsegment"].ptr,
-             ctypes.c_uint8(MKT_BUILDING), self.cust_keys.ptr,
-             self.cust_head.ptr, c_u64(self.cust_cap),
-             self.cbloom.ptr, c_u64(self.cbloom_bits - 1))
-        call("qk_q3_build_orders", sh, c_u64(self._ord_cols["o_orderkey"].n),
-             self._ord_cols["o_orderkey"].ptr,
-             self._ord_cols["o_custkey"].ptr,
-             self._ord_cols["o_orderdate"].ptr, ctypes.c_int32(Q3_DATE),
-             self.cust_keys.ptr, self.cust_head.ptr, c_u64(self.cust_cap),
-             self.ord_keys.ptr, self.ord_head.ptr, c_u64(self.ord_cap),
-             self.bloom.ptr, c_u64(self.bloom_bits - 1),
-             self.cbloom.ptr, c_u64(self.cbloom_bits - 1))
+        self._build()
 
     def probe(self, li_cols, match_count_buf=None, nt=True):
         """The fused filter+probe+group-by-aggregate pass (one kernel).
         nt=True streams the lineitem columns with non-temporal loads;
         nt=4 uses the 4-rows-per-lane ILP variant (A/B, profiles/r02)."""
         sh = self.stream.handle if self.stream else None
-        n = li_cols["l_orderkey"].n
+        common = (sh, c_u64(li_cols["l_orderkey"].n),
+                  li_cols["l_orderkey"].ptr, li_cols["l_shipdate"].ptr,
+                  li_cols["l_extendedprice"].ptr, li_cols["l_discount"].ptr,
+                  ctypes.c_int32(Q3_DATE), *self.ord.args, self.ord_sums.ptr,
+                  match_count_buf.ptr if match_count_buf else None)
         if nt == 4:
-            call("qk_q3_probe_agg_nt4", sh, c_u64(n),
-                 li_cols["l_orderkey"].ptr, li_cols["l_shipdate"].ptr,
-                 li_cols["l_extendedprice"].ptr, li_cols["l_discount"].ptr,
-                 ctypes.c_int32(Q3_DATE), self.ord_keys.ptr,
-                 self.ord_head.ptr, c_u64(self.ord_cap), self.ord_sums.ptr,
-                 match_count_buf.ptr if match_count_buf else None,
-                 self.bloom.ptr, c_u64(self.bloom_bits - 1))
+            call("qk_q3_probe_agg_nt4", *common, *self.ord.bloom_args)
         elif nt:
-            call("qk_q3_probe_agg_nt", sh, c_u64(n),
-                 li_cols["l_orderkey"].ptr, li_cols["l_shipdate"].ptr,
-                 li_cols["l_extendedprice"].ptr, li_cols["l_discount"].ptr,
-                 ctypes.c_int32(Q3_DATE), self.ord_keys.ptr,
-                 self.ord_head.ptr, c_u64(self.ord_cap), self.ord_sums.ptr,
-                 match_count_buf.ptr if match_count_buf else None,
-                 self.bloom.ptr, c_u64(self.bloom_bits - 1))
+            call("qk_q3_probe_agg_nt", *common, *self.ord.bloom_args)
         else:
-            call("qk_q3_probe_agg", sh, c_u64(n),
-                 li_cols["l_orderkey"].ptr, li_cols["l_shipdate"].ptr,
-                 li_cols["l_extendedprice"].ptr, li_cols["l_discount"].ptr,
-                 ctypes.c_int32(Q3_DATE), self.ord_keys.ptr,
-                 self.ord_head.ptr, c_u64(self.ord_cap), self.ord_sums.ptr,
-                 match_count_buf.ptr if match_count_buf else None)
+            call("qk_q3_probe_agg", *common)
 
-    def extract(self, limit=10):
-        from . import ops
-        from .shim import DevColumn, c_u64
+    def _extract_groups(self):
+        """Compact the groups with a nonzero sum into the (key, build row,
+        sum) device columns kept in _ext; returns (count, *columns)."""
         sh = self.stream.handle if self.stream else None
         out_cap = self.ord_cap
         if getattr(self, "_ext", None) is None:
@@ -343,6 +345,10 @@ class Q3Fused:
             self.stream.sync()
         k = ops._read_u64(cur)
         cur.free()
+        return k, ok, orow, osum
+
+    def extract(self, limit=10):
+        k, ok, orow, osum = self._extract_groups()
         keys = ok.to_numpy(k)
         rows = orow.to_numpy(k)
         sums = osum.to_numpy(k)
@@ -368,23 +374,7 @@ class Q3Fused:
         """Bench-lean extract: d2h only the revenue column, select the
         top-k candidates host-side, gather the candidates' key/date/prio
         on-device. Returns (n_groups, top10 dict)."""
-        from . import ops
-        from .shim import DevColumn, c_u64
-        sh = self.stream.handle if self.stream else None
-        out_cap = self.ord_cap
-        if getattr(self, "_ext", None) is None:
-            self._ext = (DevColumn(np.int64, out_cap),
-                         DevColumn(np.int32, out_cap),
-                         DevColumn(np.float64, out_cap))
-        ok, orow, osum = self._ext
-        cur = ops._count_buf()
-        call("qk_q3_extract", sh, self.ord_keys.ptr, self.ord_head.ptr,
-             self.ord_sums.ptr, c_u64(self.ord_cap), ok.ptr, orow.ptr,
-             osum.ptr, c_u64(out_cap), cur.ptr)
-        if self.stream:
-            self.stream.sync()
-        k = ops._read_u64(cur)
-        cur.free()
+        k, ok, orow, osum = self._extract_groups()
         if k == 0:
             empty = {c: np.empty(0) for c in
                      ("l_orderkey", "o_orderdate", "o_shippriority",
@@ -419,8 +409,7 @@ class Q3Fused:
         return int(k), top10
 
     def free(self):
-        for c in (self.cust_keys, self.cust_head, self.ord_keys,
-                  self.ord_head, self.ord_sums, self.bloom, self.cbloom):
+        for c in (self.cust, self.ord, self.ord_sums):
             c.free()
         if getattr(self, "_ext", None):
             for c in self._ext:
@@ -460,138 +449,92 @@ class Q5Fused:
 
     def __init__(self, ord_cols, cust_cols, supp_cols, stream=None,
                  nation_region=NATION_REGION, region=REGION_ASIA):
-        from . import shim, ops
-        from .shim import DevColumn, c_u64, c_i64
         self.stream = stream
-        sh = stream.handle if stream else None
+        self._ord_cols = ord_cols
+        self._cust_cols = cust_cols
+        self._supp_cols = supp_cols
         mask = 0
         for nk, r in enumerate(nation_region):
             if r == region:
                 mask |= 1 << nk
         self.asia_mask = mask
-
         ncust = cust_cols["c_custkey"].n
-        nsupp = supp_cols["s_suppkey"].n
-        nord = ord_cols["o_orderkey"].n
         # customer table sized by expected survivors (1/5 of nations)
-        self.cust_cap = ops._pow2_at_least(max(16, 2 * max(1, ncust // 2)))
-        self.cust_keys = DevColumn(np.int64, self.cust_cap)
-        self.cust_val = DevColumn(np.int32, self.cust_cap)
-        self.cbloom_bits = ops._pow2_at_least(max(1 << 16, 4 * ncust))
-        self.cbloom = DevColumn(np.uint32, self.cbloom_bits // 32)
-        call("qk_dmemset", self.cbloom.ptr, 0, c_u64(self.cbloom_bits // 8))
-        call("qk_fill_i64", sh, self.cust_keys.ptr,
-             c_i64(int(shim.JOIN_EMPTY)), c_u64(self.cust_cap))
-        call("qk_build_keyval_i32", sh, c_u64(ncust),
-             cust_cols["c_custkey"].ptr, cust_cols["c_nationkey"].ptr,
-             ctypes.c_uint32(mask), self.cust_keys.ptr, self.cust_val.ptr,
-             c_u64(self.cust_cap), self.cbloom.ptr,
-             c_u64(self.cbloom_bits - 1))
-        # supplier table: all rows
-        self.supp_cap = ops._pow2_at_least(max(16, 2 * nsupp))
-        self.supp_keys = DevColumn(np.int64, self.supp_cap)
-        self.supp_val = DevColumn(np.int32, self.supp_cap)
-        call("qk_fill_i64", sh, self.supp_keys.ptr,
-             c_i64(int(shim.JOIN_EMPTY)), c_u64(self.supp_cap))
-        call("qk_build_keyval_i32", sh, c_u64(nsupp),
-             supp_cols["s_suppkey"].ptr, supp_cols["s_nationkey"].ptr,
-             ctypes.c_uint32(0xFFFFFFFF), self.supp_keys.ptr,
-             self.supp_val.ptr, c_u64(self.supp_cap), None, c_u64(0))
-        # orders: count survivors -> tight table -> build
+        self.cust = _KeyTable(
+            ops._pow2_at_least(max(16, 2 * max(1, ncust // 2))),
+            ops._pow2_at_least(max(1 << 16, 4 * ncust)))
+        self.cust_cap = self.cust.cap
+        # supplier table: all rows, no prefilter
+        self.supp = _KeyTable(
+            ops._pow2_at_least(max(16, 2 * supp_cols["s_suppkey"].n)))
+        self.ord = None
+        self.out25 = DevBuffer(32 * 8)
+        self._build()
+
+    def _orders_pass(self, sh, table_args, count_ptr, bloom_args):
+        """qk_q5_build_orders: inserts into the orders table, or only
+        counts the survivors when table_args carries no table."""
+        oc = self._ord_cols
+        call("qk_q5_build_orders", sh, c_u64(oc["o_orderkey"].n),
+             oc["o_orderkey"].ptr, oc["o_custkey"].ptr, oc["o_orderdate"].ptr,
+             ctypes.c_int32(Q5_LO), ctypes.c_int32(Q5_HI), *self.cust.args,
+             *table_args, count_ptr, *bloom_args, *self.cust.bloom_args)
+
+    def _alloc_orders(self, sh):
+        """Count the survivors (needs the built customer table), then
+        size the orders table and its Bloom filter from the count."""
         cnt = ops._count_buf()
-        call("qk_q5_build_orders", sh, c_u64(nord),
-             ord_cols["o_orderkey"].ptr, ord_cols["o_custkey"].ptr,
-             ord_cols["o_orderdate"].ptr, ctypes.c_int32(Q5_LO),
-             ctypes.c_int32(Q5_HI), self.cust_keys.ptr, self.cust_val.ptr,
-             c_u64(self.cust_cap), None, None, c_u64(16), cnt.ptr, None,
-             c_u64(0), self.cbloom.ptr, c_u64(self.cbloom_bits - 1))
-        if stream:
-            stream.sync()
+        self._orders_pass(sh, (None, None, c_u64(16)), cnt.ptr,
+                          (None, c_u64(0)))
+        if self.stream:
+            self.stream.sync()
         self.n_build = ops._read_u64(cnt)
         cnt.free()
-        import os
-        lf = int(os.environ.get("QK_TABLE_LF", "4"))
-        self.ord_cap = ops._pow2_at_least(max(16, lf * self.n_build))
-        self.ord_keys = DevColumn(np.int64, self.ord_cap)
-        self.ord_val = DevColumn(np.int32, self.ord_cap)
-        self.bloom_bits = ops._pow2_at_least(max(1 << 16, 8 * self.n_build))
-        self.bloom = DevColumn(np.uint32, self.bloom_bits // 32)
-        call("qk_dmemset", self.bloom.ptr, 0, c_u64(self.bloom_bits // 8))
-        call("qk_fill_i64", sh, self.ord_keys.ptr,
-             c_i64(int(shim.JOIN_EMPTY)), c_u64(self.ord_cap))
-        call("qk_q5_build_orders", sh, c_u64(nord),
-             ord_cols["o_orderkey"].ptr, ord_cols["o_custkey"].ptr,
-             ord_cols["o_orderdate"].ptr, ctypes.c_int32(Q5_LO),
-             ctypes.c_int32(Q5_HI), self.cust_keys.ptr, self.cust_val.ptr,
-             c_u64(self.cust_cap), self.ord_keys.ptr, self.ord_val.ptr,
-             c_u64(self.ord_cap), None, self.bloom.ptr,
-             c_u64(self.bloom_bits - 1), self.cbloom.ptr,
-             c_u64(self.cbloom_bits - 1))
-        self.out25 = DevBuffer(32 * 8)
-        call("qk_dmemset", self.out25.ptr, 0, c_u64(32 * 8))
-        self._ord_cols = ord_cols
-        self._cust_cols = cust_cols
-        self._supp_cols = supp_cols
+        self.ord = _KeyTable(
+            ops._pow2_at_least(max(16, _table_lf() * self.n_build)),
+            ops._pow2_at_least(max(1 << 16, 8 * self.n_build)))
+        self.ord_cap, self.ord_keys = self.ord.cap, self.ord.keys
+        self.bloom, self.bloom_bits = self.ord.bloom, self.ord.bloom_bits
+        self.ord.clear(sh)
+
+    def _build(self):
+        """Clear the tables and run all three build passes; the first call
+        also sizes and allocates the orders table before its pass."""
+        sh = self.stream.handle if self.stream else None
+        for t in (self.cust, self.supp, self.ord):
+            if t:
+                t.clear(sh)
+        self.reset_sums()
+        for t, cols, key, val, accept in (
+                (self.cust, self._cust_cols, "c_custkey", "c_nationkey",
+                 self.asia_mask),
+                (self.supp, self._supp_cols, "s_suppkey", "s_nationkey",
+                 0xFFFFFFFF)):
+            call("qk_build_keyval_i32", sh, c_u64(cols[key].n), cols[key].ptr,
+                 cols[val].ptr, ctypes.c_uint32(accept), *t.args,
+                 *t.bloom_args)
+        if self.ord is None:
+            self._alloc_orders(sh)
+        self._orders_pass(sh, self.ord.args, None, self.ord.bloom_args)
 
     def reset_sums(self):
         call("qk_dmemset", self.out25.ptr, 0, c_u64(32 * 8))
 
     def rebuild(self):
         """Re-run all three build passes (per-step full-query semantics)."""
-        from . import shim
-        from .shim import c_u64, c_i64
-        sh = self.stream.handle if self.stream else None
-        for keys, cap in ((self.cust_keys, self.cust_cap),
-                          (self.supp_keys, self.supp_cap),
-                          (self.ord_keys, self.ord_cap)):
-            call("qk_fill_i64", sh, keys.ptr, c_i64(int(shim.JOIN_EMPTY)),
-                 c_u64(cap))
-        call("qk_dmemset", self.out25.ptr, 0, c_u64(32 * 8))
-        call("qk_dmemset", self.cbloom.ptr, 0, c_u64(self.cbloom_bits // 8))
-        call("qk_build_keyval_i32", sh,
-             c_u64(self._cust_cols["c_custkey"].n),
-             self._cust_cols["c_custkey"].ptr,
-             self._cust_cols["c_nationkey"].ptr,
-             ctypes.c_uint32(self.asia_mask), self.cust_keys.ptr,
-             self.cust_val.ptr, c_u64(self.cust_cap),
-             self.cbloom.ptr, c_u64(self.cbloom_bits - 1))
-        call("qk_build_keyval_i32", sh,
-             c_u64(self._supp_cols["s_suppkey"].n),
-             self._supp_cols["s_suppkey"].ptr,
-             self._supp_cols["s_nationkey"].ptr,
-             ctypes.c_uint32(0xFFFFFFFF), self.supp_keys.ptr,
-             self.supp_val.ptr, c_u64(self.supp_cap), None, c_u64(0))
-        call("qk_dmemset", self.bloom.ptr, 0, c_u64(self.bloom_bits // 8))
-        call("qk_q5_build_orders", sh, c_u64(self._ord_cols["o_orderkey"].n),
-             self._ord_cols["o_orderkey"].ptr,
-             self._ord_cols["o_custkey"].ptr,
-             self._ord_cols["o_orderdate"].ptr, ctypes.c_int32(Q5_LO),
-             ctypes.c_int32(Q5_HI), self.cust_keys.ptr, self.cust_val.ptr,
-             c_u64(self.cust_cap), self.ord_keys.ptr, self.ord_val.ptr,
-             c_u64(self.ord_cap), None, self.bloom.ptr,
-             c_u64(self.bloom_bits - 1), self.cbloom.ptr,
-             c_u64(self.cbloom_bits - 1))
+        self._build()
 
     def probe(self, li_cols, match_count_buf=None, nt=True):
         sh = self.stream.handle if self.stream else None
-        n = li_cols["l_orderkey"].n
+        common = (sh, c_u64(li_cols["l_orderkey"].n),
+                  li_cols["l_orderkey"].ptr, li_cols["l_suppkey"].ptr,
+                  li_cols["l_extendedprice"].ptr, li_cols["l_discount"].ptr,
+                  *self.ord.args, *self.supp.args, self.out25.ptr,
+                  match_count_buf.ptr if match_count_buf else None)
         if nt:
-            call("qk_q5_probe_agg_nt", sh, c_u64(n),
-                 li_cols["l_orderkey"].ptr, li_cols["l_suppkey"].ptr,
-                 li_cols["l_extendedprice"].ptr, li_cols["l_discount"].ptr,
-                 self.ord_keys.ptr, self.ord_val.ptr, c_u64(self.ord_cap),
-                 self.supp_keys.ptr, self.supp_val.ptr,
-                 c_u64(self.supp_cap), self.out25.ptr,
-                 match_count_buf.ptr if match_count_buf else None,
-                 self.bloom.ptr, c_u64(self.bloom_bits - 1))
-            return
-        call("qk_q5_probe_agg", sh,
-             c_u64(n), li_cols["l_orderkey"].ptr,
-             li_cols["l_suppkey"].ptr, li_cols["l_extendedprice"].ptr,
-             li_cols["l_discount"].ptr, self.ord_keys.ptr,
-             self.ord_val.ptr, c_u64(self.ord_cap), self.supp_keys.ptr,
-             self.supp_val.ptr, c_u64(self.supp_cap), self.out25.ptr,
-             match_count_buf.ptr if match_count_buf else None)
+            call("qk_q5_probe_agg_nt", *common, *self.ord.bloom_args)
+        else:
+            call("qk_q5_probe_agg", *common)
 
     def result(self):
         """[(n_name, revenue)] for ASIA nations, revenue desc
@@ -607,11 +550,8 @@ class Q5Fused:
         return out
 
     def free(self):
-        for c in (self.cust_keys, self.cust_val, self.supp_keys,
-                  self.supp_val, self.ord_keys, self.ord_val, self.bloom,
-                  self.cbloom):
+        for c in (self.cust, self.supp, self.ord, self.out25):
             c.free()
-        self.out25.free()
 
 
 def q5_fused(li_cols, ord_cols, cust_cols, supp_cols, stream=None):
