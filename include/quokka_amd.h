@@ -492,6 +492,50 @@ int qk_pq_plain_copy(void *stream, uint64_t ntiles, const uint64_t *tiles,
  * >= 8 bytes of slack after the end. */
 int qk_pq_rle_pages(void *stream, uint64_t npages, const uint64_t *ents,
                     const uint8_t *src_bytes, uint32_t *out);
+
+/* ---- nullable columns: validity bitmaps ------------------------------ *
+ * A nullable column is a dense value column of n rows (null slots hold 0)
+ * plus a validity bitmap in Arrow layout: bit i lives in byte i >> 3, LSB
+ * first, 1 = valid. The bitmap buffer is 8-byte aligned, sized up to a
+ * multiple of 8 bytes plus 8 bytes of slack, and every bit at an index
+ * >= n is 0 (kernels popcount whole 64-bit words without a tail mask).
+ * Null join keys, null group keys and null strings are not supported.
+ *
+ * qk_pq_def_pages: definition levels of a flat column (max_def == 1, bit
+ * width 1, RLE/bit-packed hybrid) -> validity bits, one wave per page.
+ * descs = npages x 6 u64 [levels_off, page_end, v2_levels_len,
+ * first_row, num_values, 0], offsets into src_dev. v2_levels_len ==
+ * UINT64_MAX marks a v1 page, whose block starts with its own [u32 len]
+ * prefix; a v2 page's levels have no prefix and the length comes from
+ * the page header. The page's bits go to valid_dev at first_row; pages
+ * start at any row, so the first and last word of a page may be shared
+ * with the neighbouring page: those are OR-ed in atomically and
+ * valid_dev must be ZEROED before the call. Interior words are plain
+ * stores. out_dev = npages x 4 i64 [non_null_count, values_off (absolute,
+ * first byte after the levels), err, first_value_byte (the bit width of an
+ * RLE_DICTIONARY page; -1 when the page has no value bytes, as an
+ * all-null page may)]; err: 0 ok, 1 levels run past the
+ * page, 2 stream truncated, 3 a level above 1. A corrupt stream ends
+ * with an error code, never a spin or a read past page_end. */
+int qk_pq_def_pages(void *stream, uint64_t npages, const uint64_t *descs_dev,
+                    const uint8_t *src_dev, uint64_t *valid_dev,
+                    int64_t *out_dev);
+/* Inverse of compaction: out[row] = valid[row] ? dense[rank(row)] : 0,
+ * rank = number of valid rows before `row`. Parquet stores only the
+ * non-null values; dense_dev holds popcount(valid) of them. elem_size 4
+ * or 8. */
+int qk_valid_expand(void *stream, uint64_t n, const uint64_t *valid_dev,
+                    const void *dense_dev, void *out_dev, uint32_t elem_size);
+/* bitmap -> u8 0/1 flags, out[i] = bit i (the predicate JIT reads
+ * validity as one more u8 input column) */
+int qk_valid_to_u8(void *stream, uint64_t n, const uint64_t *valid_dev,
+                   uint8_t *out);
+/* Bitmap of the rows idx[0..n_idx) selects, plus their null count ADDED
+ * to *out_null_count_dev (caller zeroes it). Writes ceil(n_idx / 64)
+ * whole words of out_valid_dev; the caller zeroes the slack behind them. */
+int qk_valid_gather(void *stream, uint64_t n_idx, const uint32_t *idx,
+                    const uint64_t *valid_dev, uint64_t *out_valid_dev,
+                    uint64_t *out_null_count_dev);
 /* ---- device string dictionary ---------------------------------------- *
  * General variable-width string keys for join/group-by (the reference
  * joins/groups on arbitrary key types via polars, sql_executors.py:
@@ -606,7 +650,9 @@ int qk_d2d(void *dst_dev, const void *src_dev, uint64_t nbytes);
  * compressed files transparently through pyarrow,
  * unordered_readers.py:51). One wave per page, pages independent.
  * descs_dev: npages x 8 u64 [src_off, src_len, dst_off,
- * uncompressed_len, mode (0 raw / 1 verify v1 def-levels max_def==1),
+ * uncompressed_len, mode (0 raw / 1 verify v1 def-levels max_def==1 /
+ * 2 v1 def-levels present and left in place for qk_pq_def_pages: the
+ * page is only decompressed, data_off_rel is 0),
  * num_values, 0, 0]; out_dev: npages x 4 i64 [data_off_rel (start of
  * values after the in-page levels block), err (0 ok / 1 corrupt /
  * 2 length mismatch / 3 nulls present), first_byte_after_levels (the

@@ -95,18 +95,32 @@ def to_pinned_numpy(col, n=None, stream=None):
 
 def column_to_arrow(col, n=None, stream=None):
     """One DevColumn -> pyarrow.Array over a pinned buffer (single DMA,
-    zero host copies)."""
+    zero host copies). An ops.NullableColumn keeps its nulls: the device
+    bitmap is already in Arrow's validity layout, so it is copied to a
+    pinned buffer like the values and wrapped as the validity buffer."""
     import pyarrow as pa
+    from .ops import NullableColumn
     n = col.n if n is None else int(n)
     pin = PinnedArray(col.dtype, n)
+    sh = stream.handle if stream else None
+    vbuf, null_count = None, -1       # -1: pyarrow's own default
+    if isinstance(col, NullableColumn):
+        if n != col.n:
+            raise ValueError("a NullableColumn converts whole (n=%d, "
+                             "asked %d)" % (col.n, n))
+        null_count = col.null_count
+        vpin = PinnedArray(np.uint8, (n + 7) // 8)
+        if n:
+            shim.call("qk_d2h_async", sh, vpin.ptr, col.valid.ptr,
+                      c_u64((n + 7) // 8))
+        vbuf = pa.py_buffer(vpin.arr)
     if n:
-        sh = stream.handle if stream else None
         shim.call("qk_d2h_async", sh, pin.ptr, col.ptr,
                   c_u64(n * col.dtype.itemsize))
         shim.call("qk_stream_sync", sh)
     return pa.Array.from_buffers(
         pa.from_numpy_dtype(col.dtype), n,
-        [None, pa.py_buffer(pin.arr)])
+        [vbuf, pa.py_buffer(pin.arr)], null_count=null_count)
 
 
 def table_to_arrow(cols, stream=None):

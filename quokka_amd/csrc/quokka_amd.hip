@@ -2507,6 +2507,285 @@ extern "C" int qk_pq_rle_pages(void *stream, uint64_t npages,
   return 0;
 }
 
+// ---- nullable columns: validity bitmaps ---------------------------------
+// Arrow validity layout (include/quokka_amd.h): bit i in byte i >> 3, LSB
+// first, 1 = valid; kernels address it as 64-bit words (word i >> 6, bit
+// i & 63 — the same bytes on this little-endian target). Every bit at an
+// index >= n is 0, so whole-word popcounts need no tail mask.
+//
+// k_pq_def_pages: one WAVE per page, as k_pq_rle_pages. Lane 0 parses each
+// run header of the definition-level stream (bit width 1), __shfl
+// broadcasts it, and the wave turns 64 levels per step into one __ballot
+// word. Pages start at any row, so a bitmap word can belong to two pages
+// (two waves): the wave collects a word in `acc` across its runs and
+// writes it with a plain store when the page owns all 64 rows of it,
+// and with atomicOr (into the pre-zeroed bitmap) when it is the page's
+// first or last, partly owned, word.
+// Both loops are bounded: the run loop by pos < end and remaining, the
+// varint loop by npos < end; every header advances pos by >= 1 byte.
+#define QK_DEF_ERR_PAST_PAGE 1
+#define QK_DEF_ERR_TRUNCATED 2
+#define QK_DEF_ERR_LEVEL 3
+__global__ void __launch_bounds__(WAVE) k_pq_def_pages(
+    uint64_t npages, const uint64_t *__restrict__ descs,
+    const uint8_t *__restrict__ src, uint64_t *__restrict__ valid,
+    int64_t *__restrict__ out) {
+  const uint32_t lane = threadIdx.x;
+  for (uint64_t pg = blockIdx.x; pg < npages; pg += gridDim.x) {
+    const uint64_t *D = descs + pg * 6;
+    uint64_t pos = D[0], page_end = D[1], v2_len = D[2];
+    const uint64_t row0 = D[3], page_rows = D[4];
+    uint64_t row = row0, remaining = page_rows;
+    int64_t *O = out + pg * 4;
+    int err = 0;
+    uint64_t end;
+    if (v2_len == ~0ull) {               // v1: [u32 len] prefix
+      if (pos > page_end || page_end - pos < 4) {
+        err = QK_DEF_ERR_PAST_PAGE;
+        end = pos;
+      } else {
+        uint64_t ln = (uint64_t)src[pos] | ((uint64_t)src[pos + 1] << 8) |
+                      ((uint64_t)src[pos + 2] << 16) |
+                      ((uint64_t)src[pos + 3] << 24);
+        pos += 4;
+        end = pos + ln;
+        if (end > page_end) err = QK_DEF_ERR_PAST_PAGE;
+      }
+    } else {                             // v2: length from the page header
+      end = pos + v2_len;
+      if (pos > page_end || v2_len > page_end - pos)
+        err = QK_DEF_ERR_PAST_PAGE;
+    }
+    uint64_t acc = 0, nonnull = 0;       // wave-uniform
+    while (!err && remaining && pos < end) {
+      uint64_t h = 0, npos = pos;
+      uint32_t val = 0, bad = 0;
+      if (lane == 0) {
+        uint32_t shift = 0;
+        bad = QK_DEF_ERR_TRUNCATED;      // cleared by a terminating byte
+        while (npos < end && shift < 64) {
+          uint8_t b = src[npos++];
+          h |= (uint64_t)(b & 0x7F) << shift;
+          shift += 7;
+          if (!(b & 0x80)) { bad = 0; break; }
+        }
+        if (!bad && !(h & 1)) {
+          if (npos >= end) bad = QK_DEF_ERR_TRUNCATED;
+          else {
+            val = src[npos++];
+            if (val > 1) bad = QK_DEF_ERR_LEVEL;
+          }
+        }
+      }
+      h = (uint64_t)__shfl((long long)h, 0);
+      npos = (uint64_t)__shfl((long long)npos, 0);
+      val = (uint32_t)__shfl((int)val, 0);
+      bad = (uint32_t)__shfl((int)bad, 0);
+      if (bad) { err = (int)bad; break; }
+      uint64_t n;
+      const bool packed = h & 1;
+      const uint64_t bytes0 = npos;      // bit-packed level bytes
+      if (packed) {
+        uint64_t ngroups = h >> 1;
+        if (ngroups > end - npos) { err = QK_DEF_ERR_TRUNCATED; break; }
+        n = qk_min_u64(ngroups * 8, remaining);
+        npos += ngroups;
+      } else {
+        n = qk_min_u64(h >> 1, remaining);
+      }
+      // rows [row, row + n), one bitmap word per step
+      const uint64_t rend = row + n;
+      for (uint64_t w = row >> 6; n && w <= (rend - 1) >> 6; w++) {
+        uint64_t r = (w << 6) + lane;
+        bool bit = false;
+        if (r >= row && r < rend) {
+          if (packed) {
+            uint64_t i = r - row;        // < n <= ngroups * 8
+            bit = (src[bytes0 + (i >> 3)] >> (i & 7)) & 1;
+          } else {
+            bit = val != 0;
+          }
+        }
+        uint64_t m = __ballot(bit);
+        acc |= m;
+        nonnull += __popcll(m);
+        if (rend >= (w + 1) << 6) {      // word complete for this page
+          if (lane == 0) {
+            if ((w << 6) >= row0) valid[w] = acc;
+            else if (acc) atomicOr((unsigned long long *)&valid[w],
+                                   (unsigned long long)acc);
+          }
+          acc = 0;
+        }
+      }
+      row = rend;
+      remaining -= n;
+      pos = npos;
+    }
+    if (!err && remaining) err = QK_DEF_ERR_TRUNCATED;
+    // the page's last, partly owned word
+    if (!err && acc && lane == 0)
+      atomicOr((unsigned long long *)&valid[(row0 + page_rows - 1) >> 6],
+               (unsigned long long)acc);
+    if (lane == 0) {
+      O[0] = (int64_t)nonnull;
+      O[1] = (int64_t)end;
+      O[2] = err;
+      // first value byte (an RLE_DICTIONARY page's bit width); an
+      // all-null page may have no value bytes at all
+      O[3] = (!err && end < page_end) ? (int64_t)src[end] : -1;
+    }
+  }
+}
+extern "C" int qk_pq_def_pages(void *stream, uint64_t npages,
+                               const uint64_t *descs_dev,
+                               const uint8_t *src_dev, uint64_t *valid_dev,
+                               int64_t *out_dev) {
+  if (!npages) return 0;
+  uint32_t blocks = (uint32_t)qk_min_u64(64 * 1024, npages);
+  hipLaunchKernelGGL(k_pq_def_pages, dim3(blocks), dim3(WAVE), 0,
+                     (hipStream_t)stream, npages, descs_dev, src_dev,
+                     valid_dev, out_dev);
+  QK_TRY("qk_pq_def_pages", hipGetLastError());
+  return 0;
+}
+
+// qk_valid_expand: the inverse of the filter compaction, in its count /
+// scan / write shape. Parquet stores only the non-null values, densely:
+// out[row] = valid[row] ? dense[rank(row)] : 0, rank = exclusive popcount
+// prefix of the bitmap. `chunk` (rows per block) is a multiple of BLOCK,
+// so every wave step covers exactly one bitmap word.
+__global__ void __launch_bounds__(BLOCK) k_valid_count(
+    uint64_t nwords, const uint64_t *__restrict__ valid, uint64_t chunk_words,
+    uint64_t *__restrict__ block_counts) {
+  uint64_t lo = (uint64_t)blockIdx.x * chunk_words;
+  uint64_t hi = qk_min_u64(nwords, lo + chunk_words);
+  uint32_t cnt = 0;
+  for (uint64_t w = lo + threadIdx.x; w < hi; w += BLOCK)
+    cnt += __popcll(valid[w]);
+  uint64_t s = block_sum(cnt);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = s;
+}
+template <typename T>
+__global__ void __launch_bounds__(BLOCK) k_valid_expand(
+    uint64_t n, const uint64_t *__restrict__ valid,
+    const T *__restrict__ dense, uint64_t chunk,
+    const uint64_t *__restrict__ block_offsets, T *__restrict__ out) {
+  uint64_t lo = (uint64_t)blockIdx.x * chunk;
+  uint64_t hi = qk_min_u64(n, lo + chunk);
+  __shared__ uint64_t base;
+  __shared__ uint32_t wave_tot[BLOCK / WAVE];
+  if (threadIdx.x == 0) base = block_offsets[blockIdx.x];
+  __syncthreads();
+  int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+  for (uint64_t r0 = lo; r0 < hi; r0 += BLOCK) {
+    uint64_t r = r0 + threadIdx.x;
+    uint64_t wave_row = r0 + (uint64_t)wid * WAVE;
+    // bits >= n are 0, so a word that straddles n needs no mask; a wave
+    // wholly past hi reads nothing
+    uint64_t mask = wave_row < hi ? valid[wave_row >> 6] : 0;
+    bool set = (mask >> lane) & 1;
+    uint32_t rank = __popcll(mask & ((1ULL << lane) - 1));
+    if (lane == 0) wave_tot[wid] = __popcll(mask);
+    __syncthreads();
+    uint32_t wbase = 0;
+    for (int w = 0; w < wid; w++) wbase += wave_tot[w];
+    if (r < hi) out[r] = set ? dense[base + wbase + rank] : (T)0;
+    uint32_t btot = 0;
+    for (int w = 0; w < BLOCK / WAVE; w++) btot += wave_tot[w];
+    __syncthreads();
+    if (threadIdx.x == 0) base += btot;
+    __syncthreads();
+  }
+}
+extern "C" int qk_valid_expand(void *stream, uint64_t n,
+                               const uint64_t *valid_dev,
+                               const void *dense_dev, void *out_dev,
+                               uint32_t elem_size) {
+  if (elem_size != 4 && elem_size != 8)
+    return qk_fail("qk_valid_expand.elem_size", hipErrorInvalidValue);
+  if (!n) return 0;
+  uint64_t rows_per_block = (n + MAX_BLOCKS - 1) / MAX_BLOCKS;
+  rows_per_block = ((rows_per_block + BLOCK - 1) / BLOCK) * BLOCK;
+  uint32_t blocks = (uint32_t)((n + rows_per_block - 1) / rows_per_block);
+  static __thread uint64_t *scratch = nullptr;  // block counts + total
+  if (!scratch)
+    QK_TRY("qk_valid_expand",
+           hipMalloc(&scratch, (MAX_BLOCKS + 1) * sizeof(uint64_t)));
+  hipLaunchKernelGGL(k_valid_count, dim3(blocks), dim3(BLOCK), 0,
+                     (hipStream_t)stream, (n + 63) / 64, valid_dev,
+                     rows_per_block / 64, scratch);
+  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1), 0, (hipStream_t)stream,
+                     (uint64_t)blocks, scratch, scratch + MAX_BLOCKS);
+  if (elem_size == 8)
+    hipLaunchKernelGGL(k_valid_expand<uint64_t>, dim3(blocks), dim3(BLOCK), 0,
+                       (hipStream_t)stream, n, valid_dev,
+                       (const uint64_t *)dense_dev, rows_per_block, scratch,
+                       (uint64_t *)out_dev);
+  else
+    hipLaunchKernelGGL(k_valid_expand<uint32_t>, dim3(blocks), dim3(BLOCK), 0,
+                       (hipStream_t)stream, n, valid_dev,
+                       (const uint32_t *)dense_dev, rows_per_block, scratch,
+                       (uint32_t *)out_dev);
+  QK_TRY("qk_valid_expand", hipGetLastError());
+  return 0;
+}
+
+// bitmap -> u8 0/1 flag column (the predicate JIT's validity input)
+__global__ void __launch_bounds__(BLOCK) k_valid_to_u8(
+    uint64_t n, const uint8_t *__restrict__ valid, uint8_t *__restrict__ out) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride)
+    out[i] = (valid[i >> 3] >> (i & 7)) & 1;
+}
+extern "C" int qk_valid_to_u8(void *stream, uint64_t n,
+                              const uint64_t *valid_dev, uint8_t *out) {
+  if (!n) return 0;
+  hipLaunchKernelGGL(k_valid_to_u8, dim3(qk_grid(n)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, n, (const uint8_t *)valid_dev, out);
+  QK_TRY("qk_valid_to_u8", hipGetLastError());
+  return 0;
+}
+
+// Validity of the rows idx[0..n_idx) selects: each wave step packs 64
+// gathered bits with __ballot and lane 0 stores the word (every output
+// word belongs to exactly one wave step). The loop runs on the wave's
+// first index so that all 64 lanes reach the ballot.
+__global__ void __launch_bounds__(BLOCK) k_valid_gather(
+    uint64_t n, const uint32_t *__restrict__ idx,
+    const uint8_t *__restrict__ valid, uint64_t *__restrict__ out_valid,
+    uint64_t *__restrict__ null_count) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  uint32_t lane = threadIdx.x & (WAVE - 1);
+  uint32_t nulls = 0;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x - lane;
+       i0 < n; i0 += stride) {
+    uint64_t i = i0 + lane;
+    bool bit = false;
+    if (i < n) {
+      uint32_t r = idx[i];
+      bit = (valid[r >> 3] >> (r & 7)) & 1;
+      nulls += bit ? 0u : 1u;
+    }
+    uint64_t m = __ballot(bit);
+    if (lane == 0) out_valid[i0 >> 6] = m;
+  }
+  block_add_count(nulls, null_count);
+}
+extern "C" int qk_valid_gather(void *stream, uint64_t n_idx,
+                               const uint32_t *idx, const uint64_t *valid_dev,
+                               uint64_t *out_valid_dev,
+                               uint64_t *out_null_count_dev) {
+  if (!n_idx) return 0;
+  hipLaunchKernelGGL(k_valid_gather, dim3(qk_grid(n_idx)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, n_idx, idx,
+                     (const uint8_t *)valid_dev, out_valid_dev,
+                     out_null_count_dev);
+  QK_TRY("qk_valid_gather", hipGetLastError());
+  return 0;
+}
+
 // ---- device string dictionary ------------------------------------------
 // General variable-width string keys for join/group-by (the reference
 // joins/groups on arbitrary key types via polars, sql_executors.py:
@@ -2996,8 +3275,9 @@ extern "C" int qk_d2d(void *dst, const void *src, uint64_t nbytes) {
 // parquet_gpu._check_levels_v1) and reports where the values start.
 //
 // desc per page (8 u64): [src_off, src_len, dst_off, uncompressed_len,
-//   mode (0 = raw, 1 = verify v1 def-levels for max_def 1), num_values,
-//   0, 0]
+//   mode (0 = raw, 1 = verify v1 def-levels for max_def 1, 2 = v1
+//   def-levels present but left for k_pq_def_pages: decompress only,
+//   as 0), num_values, 0, 0]
 // out per page (4 i64): [data_off_rel (after levels), err (0 ok,
 //   1 corrupt stream, 2 length mismatch, 3 nulls present),
 //   first_byte_after_levels (the RLE bit-width byte), 0]

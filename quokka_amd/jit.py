@@ -98,7 +98,8 @@ def _tokenize(s):
             out.append(_Tok("op", m.group("op")))
         else:
             w = m.group("word").upper()
-            if w in ("AND", "OR", "NOT", "BETWEEN", "IN", "LIKE"):
+            if w in ("AND", "OR", "NOT", "BETWEEN", "IN", "LIKE", "IS",
+                     "NULL"):
                 out.append(_Tok(w, w))
             else:
                 out.append(_Tok("ident", m.group("word")))
@@ -125,21 +126,68 @@ def _date_add(days, n, unit):
 
 
 class Translator:
-    """Recursive-descent predicate -> C expression over v0..vN."""
+    """Recursive-descent predicate -> C expression over v0..vN.
 
-    def __init__(self, schema, string_dicts=None):
+    With `nullable` (names of columns that may hold NULL) the predicate
+    follows SQL three-valued logic: every boolean node is lowered to a
+    pair (T = definitely true, F = definitely false) and the emitted
+    expression is the root's T, as WHERE keeps only rows that are true.
+    A nullable column's validity arrives as a synthetic u8 input
+    `__valid_<name>` (self.valid_terms), one more vK like the raw-string
+    flag columns. With no nullable column the output is the two-valued
+    string, unchanged."""
+
+    def __init__(self, schema, string_dicts=None, nullable=()):
         self.schema = schema            # name -> np dtype
         self.string_dicts = string_dicts or {}
         self.cols = []                  # referenced column names, in order
         # raw-string terms: (flag column name, column, pattern, exact);
         # each flag column is a synthetic u8 entry of self.cols
         self.str_terms = []
+        self.nullable = frozenset(nullable or ())
+        for name in self.nullable:
+            if name not in schema:
+                raise ValueError("unknown nullable column %r" % name)
+        # validity terms: (flag column name, column)
+        self.valid_terms = []
+        # nullable columns referenced since the innermost comparison began
+        self._touched = []
 
     def dtype_of(self, name):
-        """dtype of a self.cols entry (string-term flag columns are u8)."""
-        if any(t[0] == name for t in self.str_terms):
+        """dtype of a self.cols entry (string-term and validity flag
+        columns are u8)."""
+        if any(t[0] == name for t in self.str_terms) or \
+                any(t[0] == name for t in self.valid_terms):
             return np.dtype(np.uint8)
         return np.dtype(self.schema[name])
+
+    def valid_ref(self, col):
+        """-> 'vK' of the validity flag column of nullable column `col`."""
+        for name, c in self.valid_terms:
+            if c == col:
+                return "v%d" % self.cols.index(name)
+        name = "__valid_" + col
+        while name in self.schema:
+            name += "_"
+        self.valid_terms.append((name, col))
+        self.cols.append(name)
+        return "v%d" % self.cols.index(name)
+
+    def _valid_expr(self, touched):
+        """V: AND of the validity flags of the nullable columns in
+        `touched` ('' when there are none)."""
+        seen = []
+        for c in touched:
+            if c not in seen:
+                seen.append(c)
+        return " && ".join("((%s) != 0)" % self.valid_ref(c) for c in seen)
+
+    def _leaf3(self, cmp, touched):
+        """Two-valued comparison string -> (T, F)."""
+        v = self._valid_expr(touched)
+        if not v:
+            return cmp, "!(%s)" % cmp
+        return "(%s) && (%s)" % (v, cmp), "(%s) && !(%s)" % (v, cmp)
 
     def str_term_ref(self, col, pattern, exact):
         """-> 'vK' of the flag column for this term; identical terms share
@@ -185,6 +233,8 @@ class Translator:
             raise ValueError("unknown column %r" % name)
         if name not in self.cols:
             self.cols.append(name)
+        if name in self.nullable:
+            self._touched.append(name)
         return "v%d" % self.cols.index(name), self.schema[name]
 
     def translate(self, s):
@@ -193,6 +243,8 @@ class Translator:
         expr = self.p_or()
         if self.i != len(self.toks):
             raise ValueError("trailing tokens: %r" % self.toks[self.i:])
+        if self.nullable:
+            return expr[0]              # WHERE keeps the definitely-true
         return expr
 
     def peek(self):
@@ -209,27 +261,68 @@ class Translator:
         left = self.p_and()
         while self.peek() and self.peek().kind == "OR":
             self.take()
-            left = "(%s) || (%s)" % (left, self.p_and())
+            right = self.p_and()
+            if self.nullable:           # (T, F) pairs
+                left = ("(%s) || (%s)" % (left[0], right[0]),
+                        "(%s) && (%s)" % (left[1], right[1]))
+            else:
+                left = "(%s) || (%s)" % (left, right)
         return left
 
     def p_and(self):
         left = self.p_not()
         while self.peek() and self.peek().kind == "AND":
             self.take()
-            left = "(%s) && (%s)" % (left, self.p_not())
+            right = self.p_not()
+            if self.nullable:
+                left = ("(%s) && (%s)" % (left[0], right[0]),
+                        "(%s) || (%s)" % (left[1], right[1]))
+            else:
+                left = "(%s) && (%s)" % (left, right)
         return left
 
     def p_not(self):
         if self.peek() and self.peek().kind == "NOT":
             self.take()
-            return "!(%s)" % self.p_not()
+            inner = self.p_not()
+            if self.nullable:
+                return inner[1], inner[0]
+            return "!(%s)" % inner
         return self.p_cmp()
 
     def p_cmp(self):
+        """One comparison or parenthesized boolean: a C string, or its
+        (T, F) pair when there are nullable columns."""
+        outer, self._touched = self._touched, []
         try:
-            return self._p_cmp_inner()
-        except _Folded as f:
-            return f.expr
+            try:
+                res = self._p_cmp_inner()
+            except _Folded as f:
+                res = f.expr
+            if self.nullable and not isinstance(res, tuple):
+                res = self._leaf3(res, self._touched)
+            return res
+        finally:
+            self._touched = outer
+
+    def _p_is_null(self):
+        """After an arithmetic operand: 'IS [NOT] NULL' over the nullable
+        columns it references. Without any, every value is non-null and
+        the test folds to a constant."""
+        self.take("IS")
+        neg = False
+        if self.peek() and self.peek().kind == "NOT":
+            self.take()
+            neg = True
+        self.take("NULL")
+        v = self._valid_expr(self._touched)
+        if not v:
+            res = ("(0)", "(1)")
+        else:
+            res = ("!(%s)" % v, "(%s)" % v)
+        if neg:
+            res = (res[1], res[0])
+        return res if self.nullable else res[0]
 
     def _p_cmp_inner(self):
         t = self.peek()
@@ -245,12 +338,17 @@ class Translator:
                 nxt = self.peek()
                 if nxt is None or nxt.kind in ("AND", "OR") or \
                         (nxt.kind == "op" and nxt.val == ")"):
+                    if self.nullable:
+                        return "(%s)" % inner[0], "(%s)" % inner[1]
                     return "(%s)" % inner
                 raise ValueError("arith reparse")
             except ValueError:
                 self.i = save
+                self._touched = []
         left, _ = self.p_arith()
         t = self.peek()
+        if t and t.kind == "IS":
+            return self._p_is_null()
         if t and (t.kind == "IN" or
                   (t.kind == "NOT" and self.i + 1 < len(self.toks)
                    and self.toks[self.i + 1].kind == "IN")):
@@ -368,6 +466,10 @@ class Translator:
             return t.val, "strlit"   # resolved by comparison partner
         if t.kind == "ident":
             if t.val in self.schema and self.schema[t.val] == RAW_STRING:
+                if t.val in self.nullable:
+                    raise ValueError("raw string column %r is nullable: "
+                                     "null strings are not supported"
+                                     % t.val)
                 self._p_raw_string(t.val)      # raises _Folded
             ref, dtype = self.col_ref(t.val)
             # string equality: partner literal becomes the dict code
@@ -457,9 +559,11 @@ class _Folded(Exception):
         self.expr = expr
 
 
-def translate(predicate, schema, string_dicts=None):
-    """-> (c_expr, ordered column names). schema: name -> np dtype."""
-    tr = Translator(schema, string_dicts)
+def translate(predicate, schema, string_dicts=None, nullable=()):
+    """-> (c_expr, ordered column names). schema: name -> np dtype.
+    nullable: names of columns that may hold NULL (SQL three-valued
+    logic; each one referenced adds a `__valid_<name>` u8 input)."""
+    tr = Translator(schema, string_dicts, nullable)
     return tr.translate(predicate), tr.cols
 
 
@@ -483,6 +587,20 @@ def _eval_str_terms(str_terms, cols, stream):
                             "cols[%r] must be an ops.StringColumn"
                             % (col, col))
         flags[name] = ops.like(sc, pattern, exact=exact, stream=stream)
+    return flags
+
+
+def _eval_valid_terms(valid_terms, cols, stream):
+    """Expand each nullable input's bitmap (qk_valid_to_u8) ->
+    {validity flag column: DevColumn u8}."""
+    from . import ops
+    flags = {}
+    for name, col in valid_terms:
+        nc = cols[col]
+        if not isinstance(nc, ops.NullableColumn):
+            raise TypeError("column %r is declared nullable: cols[%r] "
+                            "must be an ops.NullableColumn" % (col, col))
+        flags[name] = nc.valid_flags(stream)
     return flags
 
 
@@ -511,11 +629,19 @@ class JitAggregate:
     forms the two-phase rewrite emits, sql_utils.py:299-413);
     predicate: optional filter_sql string fused into the same pass.
     run() ACCUMULATES into a DevBuffer of ngroups*naggs f64 (executor
-    state semantics, like qk_q1_agg)."""
+    state semantics, like qk_q1_agg).
+
+    nullable: names of columns that may hold NULL (run() takes an
+    ops.NullableColumn for each). The predicate follows SQL three-valued
+    logic, SUM/MIN/MAX skip rows whose expression is NULL and COUNT(expr)
+    counts the rows where it is not; COUNT(*) counts rows. A group whose
+    inputs were ALL null reads back as the aggregate's identity (0 /
+    +inf / -inf), not as NULL: put COUNT(col) beside it to tell the two
+    apart. Group keys must be non-null; a nullable one raises TypeError."""
 
     def __init__(self, schema, group_keys, aggs, predicate=None,
-                 string_dicts=None):
-        tr = Translator(schema, string_dicts)
+                 string_dicts=None, nullable=()):
+        tr = Translator(schema, string_dicts, nullable)
         pred_expr = ""
         if predicate:
             pred_expr = tr.translate(predicate)
@@ -523,6 +649,9 @@ class JitAggregate:
         self.ngroups = 1
         gparts = []
         for name, card in self.group_keys:
+            if name in tr.nullable:
+                raise TypeError("group key %r is nullable: null group keys "
+                                "are not supported" % name)
             ref, dt = tr.col_ref(name)
             if dt not in (np.dtype(np.uint8), np.dtype(np.int32)):
                 raise TypeError("group keys must be u8 code or small-"
@@ -542,17 +671,27 @@ class JitAggregate:
                 raise ValueError("unsupported aggregate %r (SUM/MIN/MAX"
                                  "(expr) / COUNT(*))" % a)
             fn, inner, alias = m.group(1).lower(), m.group(2), m.group(3)
+            tr._touched = []
             if fn == "count":
-                agg_exprs.append("1.0")
+                e = "1.0"
+                if tr.nullable and inner != "*":
+                    translate_arith(inner, schema, tr)
                 self.agg_ops.append(0)
             else:
                 e, _ = translate_arith(inner, schema, tr)
-                agg_exprs.append(e)
                 self.agg_ops.append({"sum": 0, "min": 1, "max": 2}[fn])
+            v = tr._valid_expr(tr._touched)
+            if v:
+                # a NULL input leaves the accumulator alone
+                e = "((%s) ? (double)(%s) : %s)" % (
+                    v, e, ("0.0", "(1.0/0.0)", "(-1.0/0.0)")[
+                        self.agg_ops[-1]])
+            agg_exprs.append(e)
             self.agg_names.append(alias or a.strip())
         self.naggs = len(agg_exprs)
         self.cols = tr.cols
         self.str_terms = tr.str_terms
+        self.valid_terms = tr.valid_terms
         self.dtypes = [tr.dtype_of(c) for c in self.cols]
 
         lib = shim._lib
@@ -597,6 +736,7 @@ class JitAggregate:
         lib.qk_jit_agg_run.argtypes = [c_vp, c_vp, c_u64,
                                        ctypes.POINTER(c_vp), c_vp]
         flags = _eval_str_terms(self.str_terms, cols, stream)
+        flags.update(_eval_valid_terms(self.valid_terms, cols, stream))
         if flags:
             cols = dict(cols, **flags)
         n = cols[self.cols[0]].n
@@ -673,10 +813,14 @@ class JitMap:
 class JitFilter:
     """Compiled fused filter for one predicate over a fixed schema."""
 
-    def __init__(self, predicate, schema, string_dicts=None):
-        tr = Translator(schema, string_dicts)
+    def __init__(self, predicate, schema, string_dicts=None, nullable=()):
+        """nullable: names of columns that may hold NULL; run() then takes
+        an ops.NullableColumn for each and keeps the rows for which the
+        predicate is TRUE under SQL three-valued logic."""
+        tr = Translator(schema, string_dicts, nullable)
         self.expr = tr.translate(predicate)
         self.cols, self.str_terms = tr.cols, tr.str_terms
+        self.valid_terms = tr.valid_terms
         self.dtypes = [tr.dtype_of(c) for c in self.cols]
         types = (ctypes.c_int * len(self.cols))(
             *[_TYPE_CODE[d] for d in self.dtypes])
@@ -699,6 +843,7 @@ class JitFilter:
         column). Returns (idx DevColumn u32, count)."""
         from . import ops
         flags = _eval_str_terms(self.str_terms, cols, stream)
+        flags.update(_eval_valid_terms(self.valid_terms, cols, stream))
         if flags:
             cols = dict(cols, **flags)
         n = cols[self.cols[0]].n

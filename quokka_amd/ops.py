@@ -589,6 +589,107 @@ def like(strcol, pattern, negate=False, exact=False, stream=None):
     return out
 
 
+def valid_nbytes(n):
+    """Bytes of a validity bitmap for n rows: whole 64-bit words plus 8
+    bytes of slack (include/quokka_amd.h)."""
+    return ((int(n) + 63) // 64) * 8 + 8
+
+
+def pack_valid(mask):
+    """Host bool array -> validity bitmap bytes (np.uint8, valid_nbytes
+    long, bits past the end 0)."""
+    mask = np.asarray(mask, dtype=bool)
+    out = np.zeros(valid_nbytes(len(mask)), dtype=np.uint8)
+    bits = np.packbits(mask, bitorder="little")
+    out[:len(bits)] = bits
+    return out
+
+
+class NullableColumn:
+    """A device column with SQL NULLs: `values` (DevColumn of n rows; null
+    slots hold 0, so a kernel that ignores validity still reads defined
+    data) + `valid` (DevBuffer, Arrow validity layout: bit i in byte
+    i >> 3, LSB first, 1 = valid; valid_nbytes(n) long, every bit at an
+    index >= n is 0). ptr/n/dtype delegate to `values`, so code that only
+    wants the values keeps working. Null join keys, null group keys and
+    null strings are not supported (DESIGN.md §Nullable columns)."""
+
+    def __init__(self, values, valid, n, null_count):
+        self.values = values
+        self.valid = valid
+        self.n = int(n)
+        self.null_count = int(null_count)
+
+    @property
+    def ptr(self):
+        return self.values.ptr
+
+    @property
+    def dtype(self):
+        return self.values.dtype
+
+    @classmethod
+    def from_numpy(cls, values, mask):
+        """Host values + bool mask (True = valid); null slots are zeroed."""
+        mask = np.asarray(mask, dtype=bool)
+        values = np.asarray(values)
+        values = np.where(mask, values, np.zeros(1, dtype=values.dtype))
+        bits = pack_valid(mask)
+        vb = DevBuffer(len(bits))
+        shim.call("qk_h2d", vb.ptr, bits.ctypes.data_as(c_vp),
+                  c_u64(len(bits)))
+        return cls(DevColumn.from_numpy(values), vb, len(mask),
+                   int(len(mask) - mask.sum()))
+
+    def valid_to_numpy(self):
+        """-> host bool array of n rows (True = valid)."""
+        raw = np.empty(valid_nbytes(self.n), dtype=np.uint8)
+        shim.call("qk_d2h", raw.ctypes.data_as(c_vp), self.valid.ptr,
+                  c_u64(raw.nbytes))
+        return np.unpackbits(raw, bitorder="little")[:self.n].astype(bool)
+
+    def to_numpy(self, n=None):
+        return self.values.to_numpy(n)
+
+    def valid_flags(self, stream=None):
+        """-> DevColumn u8 of 0/1 validity flags (qk_valid_to_u8)."""
+        out = DevColumn(np.uint8, max(1, self.n))
+        out.n = self.n
+        sh = stream.handle if stream else None
+        shim.call("qk_valid_to_u8", sh, c_u64(self.n), self.valid.ptr,
+                  out.ptr)
+        return out
+
+    def free(self):
+        self.values.free()
+        self.valid.free()
+
+
+def take_nullable(col, idx, n_idx=None, stream=None):
+    """col[idx] for a device u32 index column (a JitFilter result), nulls
+    kept: the existing value gather plus qk_valid_gather. `col` may be a
+    NullableColumn or a plain DevColumn (then every row is valid).
+    Returns a NullableColumn."""
+    n_idx = idx.n if n_idx is None else int(n_idx)
+    sh = stream.handle if stream else None
+    src = col.values if isinstance(col, NullableColumn) else col
+    values = src.gather(idx, n_idx, stream)
+    nb = valid_nbytes(n_idx)
+    valid = DevBuffer(nb)
+    if not isinstance(col, NullableColumn):
+        bits = pack_valid(np.ones(n_idx, dtype=bool))
+        shim.call("qk_h2d", valid.ptr, bits.ctypes.data_as(c_vp), c_u64(nb))
+        return NullableColumn(values, valid, n_idx, 0)
+    shim.call("qk_dmemset", valid.ptr, 0, c_u64(nb))
+    cnt = _count_buf()
+    shim.call("qk_valid_gather", sh, c_u64(n_idx), idx.ptr, col.valid.ptr,
+              valid.ptr, cnt.ptr)
+    shim.call("qk_stream_sync", sh)
+    nulls = _read_u64(cnt)
+    cnt.free()
+    return NullableColumn(values, valid, n_idx, nulls)
+
+
 def sort_permutation(col, stream=None, descending=False):
     """Stable sort permutation of a DevColumn (i64/f64/i32/u32 keys):
     returns a u32 DevColumn `perm` with rows in ascending (or descending)

@@ -16,8 +16,11 @@ Supported (the TPC-H hot-path column shapes):
   dictionary gathered on GPU)
 - RLE_DICTIONARY BYTE_ARRAY columns -> (u32 code column in HBM, host
   value list), the string-dictionary form the executors already use
-- flat nullable columns with NO nulls present (definition levels are
-  verified host-side from the run descriptors); actual nulls raise
+- flat nullable columns: with read_table's default nulls="raise" only
+  columns with NO nulls present decode (definition levels are verified
+  from the run descriptors) and actual nulls raise; nulls="mask" decodes
+  them into an ops.NullableColumn (values + validity bitmap, both
+  expanded on the GPU: qk_pq_def_pages, qk_valid_expand)
 
 Anything else raises QkParquetError — loudly, no CPU value fallback.
 """
@@ -132,7 +135,7 @@ class _Chunk:
     """Decode plan for one column chunk: PLAIN tiles and/or dictionary
     (values + RLE index entries), all offsets absolute into the file."""
 
-    def __init__(self, buf, col, max_def, dst0):
+    def __init__(self, buf, col, max_def, dst0, mask=False):
         if col.compression != "UNCOMPRESSED":
             raise QkParquetError("compressed chunks unsupported here (%s); "
                                  "SNAPPY goes through the GPU decompressor "
@@ -150,6 +153,13 @@ class _Chunk:
         self.rle_pages = []
         self.dict_vals = None          # np array (fixed) or list (strings)
         self.n = col.num_values
+        # mask mode, nullable column: the value plan waits for the
+        # device's per-page non-null counts (_decode_masked)
+        self.def_pages = []
+        mask = mask and max_def > 0
+        if mask and max_def != 1:
+            raise QkParquetError("nested schemas unsupported (max_def=%d)"
+                                 % max_def)
         row = dst0
         for p in T.walk_pages(buf, start, col.total_compressed_size,
                               col.num_values):
@@ -158,6 +168,11 @@ class _Chunk:
                     raise QkParquetError("dict page encoding %d"
                                          % p.encoding)
                 self._load_dict(buf, p)
+                continue
+            if mask:
+                self.def_pages.append(
+                    _def_page(p, p.data_off, p.data_len, row))
+                row += p.num_values
                 continue
             if p.kind == T.PAGE_DATA:
                 data = p.data_off
@@ -207,6 +222,16 @@ class _Chunk:
                 offset=p.data_off).copy()
 
 
+def _def_page(p, off, size, row):
+    """Mask-mode record of one data page whose `size` bytes (levels
+    first) start at `off` in the decode source: (levels_off, page_end,
+    v2 levels length or None for a v1 page, first row, num_values,
+    encoding, v2 header num_nulls or None)."""
+    v2 = p.kind != T.PAGE_DATA
+    return (off, off + size, p.v2_levels_len if v2 else None, row,
+            p.num_values, p.encoding, p.num_nulls if v2 else None)
+
+
 class _PlanChunk:
     """Duck-typed like _Chunk for _decode_column: a decode plan whose
     offsets point into the DECOMPRESSED scratch buffer instead of the
@@ -219,9 +244,11 @@ class _PlanChunk:
         self.plain_tiles = []
         self.rle_pages = []
         self.dict_vals = None
+        self.def_pages = []
 
 
-def _snappy_column(shim, raw, dev_file, cols_meta, max_def, dst0):
+def _snappy_column(shim, raw, dev_file, cols_meta, max_def, dst0,
+                   mask=False):
     """Plan + decompress one column whose chunks are SNAPPY-compressed
     (or a mix of SNAPPY and UNCOMPRESSED pages): every page's
     decompressed bytes land in one scratch DevBuffer via qk_snappy_pages
@@ -243,6 +270,9 @@ def _snappy_column(shim, raw, dev_file, cols_meta, max_def, dst0):
     is_ba = phys == "BYTE_ARRAY"
     if dtype is None and not is_ba:
         raise QkParquetError("unsupported physical type %s" % phys)
+    # mask mode, nullable column: levels stay in the scratch buffer for
+    # qk_pq_def_pages, nothing here verifies or refuses them
+    mask = mask and max_def > 0
 
     chunk_pages = []
     row = dst0
@@ -270,7 +300,8 @@ def _snappy_column(shim, raw, dev_file, cols_meta, max_def, dst0):
             # v2 pages carry is_compressed (writers leave incompressible
             # pages raw and clear it) — those route to the byte-copy path
             codec = col.compression if p.is_compressed else "UNCOMPRESSED"
-            if codec == "GZIP" and p.kind == T.PAGE_DATA and max_def > 0:
+            if codec == "GZIP" and p.kind == T.PAGE_DATA and max_def > 0 \
+                    and not mask:
                 # a nullable v1 page keeps its def-levels INSIDE the
                 # compressed stream; the gzip kernel (unlike snappy's)
                 # does not parse them — write non-nullable or v2 pages
@@ -290,7 +321,7 @@ def _snappy_column(shim, raw, dev_file, cols_meta, max_def, dst0):
                 if codec == "SNAPPY":
                     descs.append((p.data_off, p.data_len, off,
                                   p.uncompressed_len,
-                                  1 if max_def > 0 else 0,
+                                  2 if mask else 1 if max_def > 0 else 0,
                                   p.num_values, 0, 0))
                     ent["desc"] = len(descs) - 1
                 else:
@@ -310,7 +341,7 @@ def _snappy_column(shim, raw, dev_file, cols_meta, max_def, dst0):
                                    p.uncompressed_len, 1, 0, 0, 0))
                     ent["gdesc"] = len(gdescs) - 1
             else:                                  # v2: levels NOT compressed
-                if p.num_nulls:
+                if p.num_nulls and not mask:
                     raise QkParquetError("page contains nulls")
                 lv = p.v2_levels_len
                 if lv:
@@ -427,6 +458,12 @@ def _snappy_column(shim, raw, dev_file, cols_meta, max_def, dst0):
                 cur.dict_vals = np.frombuffer(
                     db, dtype=dtype, count=p.num_values).copy()
             continue
+        if mask:
+            # every kind of data page lies in the scratch at `o`, levels
+            # first: raw pages with their file length, the others with
+            # their uncompressed length
+            cur.def_pages.append(_def_page(p, o, ent["size"], ent["row"]))
+            continue
         # data pages: find where values start + the RLE bit-width byte
         if ent["kind"] == "v1":
             if ent.get("gdesc") is not None:
@@ -488,13 +525,137 @@ def _upload(shim, host_bytes):
     return buf
 
 
-def read_table(source, columns=None):
+_DEF_ERR = {1: "definition levels run past the page",
+            2: "definition levels truncated",
+            3: "definition level above 1 (nested schemas unsupported)"}
+_V1 = (1 << 64) - 1      # qk_pq_def_pages: v2_levels_len marker of a v1 page
+
+
+def _def_descs(chunks):
+    """qk_pq_def_pages descriptors (npages x 6 u64) of a mask-mode column,
+    in page order."""
+    return np.asarray(
+        [(off, end, _V1 if v2len is None else v2len, row, nv, 0)
+         for ch in chunks
+         for (off, end, v2len, row, nv, _enc, _nn) in ch.def_pages],
+        dtype=np.uint64).reshape(-1, 6)
+
+
+def _dense_plan(chunks, results):
+    """Mask mode, after qk_pq_def_pages: `results` is its per-page table
+    (npages x 4 i64 [non_null, values_off, err, first_value_byte]).
+    Fills each chunk's plain_tiles / rle_pages so that every page decodes
+    its `non_null` stored values to DENSE positions (host prefix sum of
+    the per-page counts). Returns the total non-null count."""
+    dense = 0
+    k = 0
+    for ch in chunks:
+        ch.plain_tiles, ch.rle_pages = [], []
+        for (off, end, v2len, row, nv, enc, hdr_nulls) in ch.def_pages:
+            nn, voff, err, first = (int(x) for x in results[k])
+            k += 1
+            if err:
+                raise QkParquetError("page %d: %s"
+                                     % (k - 1, _DEF_ERR.get(err, err)))
+            if hdr_nulls is not None and nn != nv - hdr_nulls:
+                # v1 headers carry no null count; v2's must agree
+                raise QkParquetError(
+                    "page %d: definition levels give %d non-null values, "
+                    "the page header %d" % (k - 1, nn, nv - hdr_nulls))
+            if enc == ENC_PLAIN:
+                if ch.is_ba:
+                    raise QkParquetError("PLAIN BYTE_ARRAY unsupported; "
+                                         "write with use_dictionary=True")
+                if nn:
+                    es = ch.dtype.itemsize
+                    if voff + nn * es > end:
+                        raise QkParquetError("PLAIN values run past the "
+                                             "page")
+                    ch.plain_tiles.append(_tile_block(voff, dense, nn, es))
+            elif enc == ENC_RLE_DICT:
+                # an all-null page has no index stream, possibly not even
+                # the bit-width byte
+                if nn:
+                    if first < 0 or first > 32:
+                        raise QkParquetError("index bit width %d" % first)
+                    ch.rle_pages.append((voff + 1, end, dense, nn, first))
+            else:
+                raise QkParquetError("data page encoding %d" % enc)
+            dense += nn
+    return dense
+
+
+def _decode_masked(shim, src, chunks, total):
+    """Mask-mode decode of one nullable column from the decode source
+    `src` (file bytes or decompressed scratch): qk_pq_def_pages ->
+    validity bitmap + per-page counts, the unchanged value kernels into a
+    dense temporary, qk_valid_expand into the row-aligned column.
+    Returns an ops.NullableColumn — a plain DevColumn when no row is
+    null — or (that, values list) for BYTE_ARRAY dictionary columns."""
+    import ctypes
+    from .ops import NullableColumn, valid_nbytes
+    from .shim import DevBuffer, DevColumn, c_u64, c_vp
+    descs = _def_descs(chunks)
+    npages = len(descs)
+    if npages and int((descs[:, 3] + descs[:, 4]).max()) > total:
+        raise QkParquetError("pages hold more rows than the file")
+    nb = valid_nbytes(total)
+    valid = DevBuffer(nb)
+    shim.call("qk_dmemset", valid.ptr, 0, c_u64(nb))
+    results = np.zeros((npages, 4), dtype=np.int64)
+    if npages:
+        dd = DevBuffer(descs.nbytes)
+        shim.call("qk_h2d", dd.ptr, descs.ctypes.data_as(c_vp),
+                  c_u64(descs.nbytes))
+        dout = DevBuffer(results.nbytes)
+        shim.call("qk_pq_def_pages", None, c_u64(npages), dd.ptr, src.ptr,
+                  valid.ptr, dout.ptr)
+        shim.call("qk_stream_sync", None)
+        shim.call("qk_d2h", results.ctypes.data_as(c_vp), dout.ptr,
+                  c_u64(results.nbytes))
+        dd.free()
+        dout.free()
+    try:
+        nonnull = _dense_plan(chunks, results)
+    except QkParquetError:
+        valid.free()
+        raise
+    dense = _decode_column(shim, src, chunks, nonnull)
+    vals = None
+    if chunks[0].is_ba:
+        dense, vals = dense
+    if nonnull == total:
+        valid.free()
+        out = dense
+    else:
+        col = DevColumn(dense.dtype, max(1, total))
+        col.n = total
+        shim.call("qk_valid_expand", None, c_u64(total), valid.ptr,
+                  dense.ptr, col.ptr, ctypes.c_uint32(dense.dtype.itemsize))
+        shim.call("qk_stream_sync", None)
+        dense.free()
+        out = NullableColumn(col, valid, total, total - nonnull)
+    return (out, vals) if vals is not None else out
+
+
+def read_table(source, columns=None, nulls="raise"):
     """Decode a Parquet file into device columns.
 
     source: path or bytes. Returns dict name -> DevColumn for fixed-width
     columns, and name -> (DevColumn u32 codes, list values) for
     dictionary-encoded BYTE_ARRAY columns (the executors' string-dict
-    form, quokka_amd/executors.py StringDict)."""
+    form, quokka_amd/executors.py StringDict).
+
+    nulls="raise" (default): a page that holds a null raises
+    QkParquetError. nulls="mask": a flat nullable column with at least
+    one null comes back as an ops.NullableColumn (null slots hold 0; for
+    a dictionary BYTE_ARRAY column the u32 codes are the NullableColumn
+    and null slots hold code 0); one without nulls still comes back as a
+    plain DevColumn."""
+    if nulls not in ("raise", "mask"):
+        raise ValueError("nulls must be 'raise' or 'mask', got %r"
+                         % (nulls,))
+    mask = nulls == "mask"
     import pyarrow.parquet as pq
     from . import shim
     from .shim import DevBuffer, DevColumn, c_u64, c_vp
@@ -556,7 +717,7 @@ def read_table(source, columns=None):
             chunks = []
             row = 0
             for col in cols_meta:
-                ch = _Chunk(raw, col, max_def, row)
+                ch = _Chunk(raw, col, max_def, row, mask)
                 row += ch.n
                 chunks.append(ch)
             assert row == total, (row, total)
@@ -564,14 +725,18 @@ def read_table(source, columns=None):
         # phase 2: device decode (first ptr access joins the upload)
         for ci in want:
             kind, payload, max_def = plans[ci]
+            masked = mask and max_def > 0
             if kind == "snappy":
                 chunks, scratch = _snappy_column(shim, raw, dev_file,
-                                                 payload, max_def, 0)
+                                                 payload, max_def, 0, mask)
                 assert sum(ch.n for ch in chunks) == total
-                out[names[ci]] = _decode_column(shim, scratch, chunks,
-                                                total)
+                decode = _decode_masked if masked else _decode_column
+                out[names[ci]] = decode(shim, scratch, chunks, total)
                 shim.call("qk_stream_sync", None)
                 scratch.free()
+            elif masked:
+                out[names[ci]] = _decode_masked(shim, dev_file, payload,
+                                                total)
             else:
                 out[names[ci]] = _decode_column(shim, dev_file, payload,
                                                 total)

@@ -77,8 +77,56 @@ def column_to_numpy(col, string_dict=None):
     return arr
 
 
-def stage_columns(table, names=None, string_dicts=None):
-    """pyarrow Table or dict-of-numpy -> dict name -> DevColumn."""
+def split_nulls(col):
+    """Host half of stage_columns' mask mode: pyarrow Array/ChunkedArray
+    with nulls -> (values filled with 0 in the null slots, so an int64
+    column stays int64; bool mask, True = valid). The mask is rebuilt
+    from the array itself, so a sliced array (non-zero offset, validity
+    bits not byte-aligned) gives the mask of its own rows."""
+    import pyarrow as pa
+    import pyarrow.compute as pc
+    if isinstance(col, pa.ChunkedArray):
+        col = col.combine_chunks()
+    mask = pc.is_valid(col).to_numpy(zero_copy_only=False)
+    t = col.type
+    if pa.types.is_date32(t):
+        col = col.cast(pa.int32())      # days, as column_to_numpy gives
+    elif pa.types.is_temporal(t):
+        raise TypeError("nulls='mask': %s columns unsupported" % t)
+    filled = col.fill_null(False if pa.types.is_boolean(t) else 0)
+    return filled, np.ascontiguousarray(mask, dtype=bool)
+
+
+def stage_columns(table, names=None, string_dicts=None, nulls="raise"):
+    """pyarrow Table or dict-of-numpy -> dict name -> DevColumn.
+
+    nulls="raise" (default) stages exactly as before. nulls="mask"
+    uploads an Arrow column that has nulls as an ops.NullableColumn
+    (values from fill_null(0), validity bitmap beside them); columns
+    without nulls still come back as plain DevColumns. Null strings stay
+    unsupported."""
+    if nulls not in ("raise", "mask"):
+        raise ValueError("nulls must be 'raise' or 'mask', got %r"
+                         % (nulls,))
+    if nulls == "mask" and not isinstance(table, dict):
+        import pyarrow as pa
+        from .ops import NullableColumn
+        out = {}
+        for name in names or table.column_names:
+            col = table.column(name)
+            sd = (string_dicts or {}).get(name)
+            if not col.null_count:
+                out[name] = DevColumn.from_numpy(column_to_numpy(col, sd))
+                continue
+            t = col.type
+            if pa.types.is_dictionary(t) or pa.types.is_string(t) or \
+                    pa.types.is_large_string(t):
+                raise TypeError("column %r: null strings unsupported"
+                                % name)
+            filled, mask = split_nulls(col)
+            out[name] = NullableColumn.from_numpy(
+                column_to_numpy(filled, sd), mask)
+        return out
     out = {}
     if isinstance(table, dict):
         items = table.items() if names is None else [(n, table[n]) for n in names]
