@@ -561,6 +561,64 @@ int qk_str_dict_rehash(void *stream, uint32_t ncodes,
                        const uint64_t *code_off, const uint32_t *code_len,
                        const uint8_t *arena, uint64_t *slot_hash,
                        int32_t *slot_code, uint64_t capacity);
+/* ---- device key dictionary (K full-width key columns) ----------------- *
+ * SQLAggExecutor groups by an arbitrary groupby_keys list inside DuckDB
+ * (sql_executors.py:556-599) and DistinctExecutor calls
+ * unique(subset=keys) (sql_executors.py:517-554). Here every key column is
+ * one 64-bit word per row, and a row's tuple of nkeys words maps to a
+ * dense u32 code that is the same in every later call (slots, key store
+ * and counter persist). No key value is reserved: INT64_MIN, 0, -1 and
+ * INT64_MAX are ordinary keys in every column.
+ *
+ * key_cols_dev: device array of nkeys pointers to i64 columns of n rows.
+ * slots: u64[capacity] (pow2), zeroed before first use. A word is 0 when
+ *   free; otherwise bits 62..32 hold a non-zero 31-bit hash tag and bits
+ *   31..0 the code. Bit 63 marks a slot claimed during the running call,
+ *   whose low half is then the claiming batch row; no such word survives a
+ *   call that reports no error. All nkeys words are compared before a slot
+ *   counts as a match; the tag only spares most of those compares.
+ * store: i64[nkeys * code_cap], column-major: word k of code c is
+ *   store[k * code_cap + c].
+ * counter_dev (u32): number of codes handed out so far.
+ * row_slot: scratch, u64[n]. out_codes: u32[n].
+ * err_dev (u32, zeroed by the caller): OR of 1 = a probe walk visited all
+ *   `capacity` slots without finding the key or a free slot, 2 = a new
+ *   code did not fit code_cap. After an error the table must be dropped.
+ * Three launches (claim, finalise, resolve); no lane waits for another
+ * lane's store, and every probe walk ends after `capacity` steps. HOST
+ * must guarantee before each call: 2 * (counter + n) <= capacity,
+ * counter + n <= code_cap, n < 2^32, counter + n < 2^32 - 1. */
+int qk_keydict_encode(void *stream, uint64_t n, int nkeys,
+                      const void *key_cols_dev /* dev int64_t*[nkeys] */,
+                      uint64_t *slots, uint64_t capacity, int64_t *store,
+                      uint64_t code_cap, uint32_t *counter_dev,
+                      uint64_t *row_slot, uint32_t *out_codes,
+                      uint32_t *err_dev);
+/* Growth: seat (hash of store[code], code) for every code < ncodes into a
+ * larger zeroed slot array. Codes and key store are not touched (the host
+ * grows the store by per-column device copies). err_dev as above (bit 1). */
+int qk_keydict_rehash(void *stream, uint32_t ncodes, int nkeys,
+                      const int64_t *store, uint64_t code_cap,
+                      uint64_t *slots, uint64_t capacity, uint32_t *err_dev);
+/* ---- dense accumulate over key-dictionary codes ----------------------- *
+ * The aggregate half of SQLAggExecutor's group-by (sql_executors.py:
+ * 556-599) once qk_keydict_encode has turned the key columns into dense
+ * codes: acc holds one record of rstride (pow2 >= nvals) doubles per code,
+ * record c at acc[c * rstride], so a row touches one line and extraction
+ * is a plain copy of the first `counter` records.
+ * qk_groupby_dense_init sets records [first, first + count) to the op
+ * identities inits_dev[nvals] (0 SUM, +inf MIN, -inf MAX; pad words 0). */
+int qk_groupby_dense_init(void *stream, double *acc, uint64_t first,
+                          uint64_t count, int rstride, int nvals,
+                          const double *inits_dev);
+/* For each row i: acc[codes[i]][c] op= vals[c][i], op per agg_ops_dev as in
+ * qk_groupby_i64_sum (NULL = all SUM). A code >= ncodes is skipped and
+ * reported as bit 4 of err_dev (u32, zeroed by the caller). */
+int qk_groupby_dense_acc(void *stream, uint64_t n, const uint32_t *codes,
+                         uint32_t ncodes,
+                         const void *vals_dev /* dev double*[nvals] */,
+                         const int32_t *agg_ops_dev, int nvals, int rstride,
+                         double *acc, uint32_t *err_dev);
 /* ---- LIKE over free-text string columns ------------------------------- *
  * The reference hands `col LIKE 'pat'` / NOT LIKE / = / <> on varchar
  * columns to DuckDB or polars inside filter_sql (core.py:157-163; the

@@ -2934,6 +2934,277 @@ extern "C" int qk_str_dict_rehash(void *stream, uint32_t ncodes,
   return 0;
 }
 
+// ---- device key dictionary: K-word keys -> dense u32 codes -------------
+// SQLAggExecutor groups by an arbitrary groupby_keys list and
+// DistinctExecutor calls unique(subset=keys) (sql_executors.py:556-599,
+// :517-554). Each key column arrives as one 64-bit word per row; a row's
+// K words map to a dense code that stays the same across batches (slot
+// array, key store and counter persist), so the aggregate is a dense
+// accumulate over the codes and extract needs no compaction.
+//
+// slots: u64[cap], 0 = empty, else
+//   bit 63      pending: claimed in THIS encode call, bits 31..0 = the
+//               claiming batch row (the key is read from the input columns)
+//   bits 62..32 tag = 31 hash bits, never 0 (a filter only: all K words are
+//               compared before a slot counts as a match)
+//   bits 31..0  code (pending clear): the key is store[k * code_cap + code]
+// No key value is reserved. No lane waits for another lane's store: the
+// claim launch only reads words that are immutable while it runs (input
+// columns, key-store entries of earlier calls), the finalise launch has one
+// writer per slot, the resolve launch only reads.
+#define QK_KD_PENDING 0x8000000000000000ULL
+#define QK_KD_NOSLOT 0xFFFFFFFFFFFFFFFFULL
+#define QK_KD_NOCODE 0xFFFFFFFFu
+
+__device__ inline uint64_t qk_kd_tag(uint64_t h) {
+  uint64_t t = (h >> 32) & 0x7FFFFFFFULL;
+  return (t ? t : 1ULL) << 32;
+}
+// splitmix64 folded over the words in order, as qk_str_hash folds 8-byte
+// chunks: (a, b) and (b, a) hash differently
+__device__ inline uint64_t qk_kd_hash_row(const int64_t *const *cols,
+                                          int nkeys, uint64_t i) {
+  uint64_t h = 0x9E3779B97F4A7C15ULL ^ (uint64_t)nkeys;
+  for (int k = 0; k < nkeys; k++) h = splitmix64(h ^ (uint64_t)cols[k][i]);
+  return h;
+}
+
+// (a) claim and record: row_slot[i] = the slot that holds row i's key
+__global__ void __launch_bounds__(BLOCK) k_keydict_claim(
+    uint64_t n, int nkeys, const int64_t *const *__restrict__ cols,
+    uint64_t *slots, uint64_t cap, const int64_t *__restrict__ store,
+    uint64_t code_cap, uint64_t *__restrict__ row_slot, uint32_t *err) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    uint64_t h = qk_kd_hash_row(cols, nkeys, i);
+    uint64_t tag = qk_kd_tag(h);
+    uint64_t mine = QK_KD_PENDING | tag | (i & 0xFFFFFFFFULL);
+    uint64_t s = h & (cap - 1);
+    uint64_t found = QK_KD_NOSLOT;
+    for (uint64_t step = 0; step < cap; step++) {
+      uint64_t cur = __atomic_load_n((unsigned long long *)&slots[s],
+                                     __ATOMIC_RELAXED);
+      if (cur == 0) {
+        cur = atomicCAS((unsigned long long *)&slots[s], 0ULL,
+                        (unsigned long long)mine);
+        if (cur == 0) {
+          found = s;
+          break;
+        }
+      }
+      if ((cur & 0x7FFFFFFF00000000ULL) == tag) {
+        uint64_t ref = cur & 0xFFFFFFFFULL;
+        // ref < n holds for every claim of this launch, ref < code_cap for
+        // every code handed out; checked so that no word can index past
+        // the columns or the store
+        bool eq;
+        if (cur & QK_KD_PENDING) {
+          eq = ref < n;
+          for (int k = 0; k < nkeys && eq; k++)
+            eq = cols[k][ref] == cols[k][i];
+        } else {
+          eq = ref < code_cap;
+          for (int k = 0; k < nkeys && eq; k++)
+            eq = store[(uint64_t)k * code_cap + ref] == cols[k][i];
+        }
+        if (eq) {
+          found = s;
+          break;
+        }
+      }
+      s = (s + 1) & (cap - 1);
+    }
+    row_slot[i] = found;
+    if (found == QK_KD_NOSLOT) atomicOr(err, 1u);
+  }
+}
+
+// (b) finalise: the claiming row of each new slot takes a dense code (one
+// atomicAdd per wave, as k_groupby_extract), copies its K words into the
+// key store and rewrites the slot as tag | code
+__global__ void __launch_bounds__(BLOCK) k_keydict_finalise(
+    uint64_t n, int nkeys, const int64_t *const *__restrict__ cols,
+    uint64_t *slots, int64_t *__restrict__ store, uint64_t code_cap,
+    const uint64_t *__restrict__ row_slot, uint32_t *counter, uint32_t *err) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  int lane = (int)(threadIdx.x & (WAVE - 1));
+  // whole waves stay in the loop (b0 is wave-uniform) for the ballot
+  for (uint64_t b0 = (uint64_t)blockIdx.x * blockDim.x; b0 < n; b0 += stride) {
+    uint64_t i = b0 + threadIdx.x;
+    uint64_t s = i < n ? row_slot[i] : QK_KD_NOSLOT;
+    uint64_t w = s != QK_KD_NOSLOT ? slots[s] : 0;
+    bool claimant = (w & QK_KD_PENDING) && (w & 0xFFFFFFFFULL) == (uint32_t)i;
+    uint64_t mask = __ballot(claimant);
+    if (!mask) continue;
+    int src = __ffsll((unsigned long long)mask) - 1;
+    uint32_t base = 0;
+    if (lane == src) base = atomicAdd(counter, (uint32_t)__popcll(mask));
+    base = __shfl(base, src);
+    if (claimant) {
+      uint64_t code = base + (uint32_t)__popcll(mask & ((1ULL << lane) - 1));
+      if (code < code_cap && code < QK_KD_NOCODE) {
+        for (int k = 0; k < nkeys; k++)
+          store[(uint64_t)k * code_cap + code] = cols[k][i];
+        slots[s] = (w & 0x7FFFFFFF00000000ULL) | code;
+      } else {
+        atomicOr(err, 2u);
+      }
+    }
+  }
+}
+
+// (c) resolve: codes[i] = the code in slot row_slot[i]
+__global__ void __launch_bounds__(BLOCK) k_keydict_resolve(
+    uint64_t n, const uint64_t *__restrict__ slots,
+    const uint64_t *__restrict__ row_slot, uint32_t *__restrict__ codes) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    uint64_t s = row_slot[i];
+    uint64_t w = s != QK_KD_NOSLOT ? slots[s] : QK_KD_PENDING;
+    codes[i] = (w & QK_KD_PENDING) ? QK_KD_NOCODE : (uint32_t)w;
+  }
+}
+
+extern "C" int qk_keydict_encode(void *stream, uint64_t n, int nkeys,
+                                 const void *key_cols_dev, uint64_t *slots,
+                                 uint64_t cap, int64_t *store,
+                                 uint64_t code_cap, uint32_t *counter_dev,
+                                 uint64_t *row_slot, uint32_t *out_codes,
+                                 uint32_t *err_dev) {
+  if (!n) return 0;
+  if (!cap || !qk_pow2(cap))
+    return qk_fail("qk_keydict_encode.cap_pow2", hipErrorInvalidValue);
+  if (nkeys < 1 || n > 0xFFFFFFFFULL)
+    return qk_fail("qk_keydict_encode.nkeys_or_n", hipErrorInvalidValue);
+  const int64_t *const *cols = (const int64_t *const *)key_cols_dev;
+  uint32_t blocks = qk_grid(n);
+  hipLaunchKernelGGL(k_keydict_claim, dim3(blocks), dim3(BLOCK), 0,
+                     (hipStream_t)stream, n, nkeys, cols, slots, cap, store,
+                     code_cap, row_slot, err_dev);
+  QK_TRY("qk_keydict_encode.claim", hipGetLastError());
+  hipLaunchKernelGGL(k_keydict_finalise, dim3(blocks), dim3(BLOCK), 0,
+                     (hipStream_t)stream, n, nkeys, cols, slots, store,
+                     code_cap, row_slot, counter_dev, err_dev);
+  QK_TRY("qk_keydict_encode.finalise", hipGetLastError());
+  hipLaunchKernelGGL(k_keydict_resolve, dim3(blocks), dim3(BLOCK), 0,
+                     (hipStream_t)stream, n, slots, row_slot, out_codes);
+  QK_TRY("qk_keydict_encode.resolve", hipGetLastError());
+  return 0;
+}
+
+// Growth: re-seat (hash(store[code]), code) into a larger zeroed slot
+// array; codes and the key store do not change.
+__global__ void __launch_bounds__(BLOCK) k_keydict_rehash(
+    uint32_t ncodes, int nkeys, const int64_t *__restrict__ store,
+    uint64_t code_cap, uint64_t *slots, uint64_t cap, uint32_t *err) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       c < ncodes; c += stride) {
+    uint64_t h = 0x9E3779B97F4A7C15ULL ^ (uint64_t)nkeys;
+    for (int k = 0; k < nkeys; k++)
+      h = splitmix64(h ^ (uint64_t)store[(uint64_t)k * code_cap + c]);
+    uint64_t word = qk_kd_tag(h) | c;
+    uint64_t s = h & (cap - 1);
+    bool seated = false;
+    for (uint64_t step = 0; step < cap && !seated; step++) {
+      seated = atomicCAS((unsigned long long *)&slots[s], 0ULL,
+                         (unsigned long long)word) == 0;
+      s = (s + 1) & (cap - 1);
+    }
+    if (!seated) atomicOr(err, 1u);
+  }
+}
+extern "C" int qk_keydict_rehash(void *stream, uint32_t ncodes, int nkeys,
+                                 const int64_t *store, uint64_t code_cap,
+                                 uint64_t *slots, uint64_t cap,
+                                 uint32_t *err_dev) {
+  if (!ncodes) return 0;
+  if (!cap || !qk_pow2(cap))
+    return qk_fail("qk_keydict_rehash.cap_pow2", hipErrorInvalidValue);
+  if (nkeys < 1 || ncodes > code_cap)
+    return qk_fail("qk_keydict_rehash.nkeys_or_ncodes", hipErrorInvalidValue);
+  hipLaunchKernelGGL(k_keydict_rehash, dim3(qk_grid(ncodes)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, ncodes, nkeys, store, code_cap,
+                     slots, cap, err_dev);
+  QK_TRY("qk_keydict_rehash", hipGetLastError());
+  return 0;
+}
+
+// ---- dense accumulate over key-dictionary codes ------------------------
+// acc: one record of rstride (pow2 >= nvals) doubles per code, so a row
+// touches one line (the interleaved records of k_groupby_sum without the
+// key word). Records [first, first + count) start at the op identities.
+__global__ void __launch_bounds__(BLOCK) k_groupby_dense_init(
+    uint64_t first, uint64_t count, int rstride, int nvals,
+    const double *__restrict__ inits, double *__restrict__ acc) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  uint64_t words = count * (uint64_t)rstride;
+  for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < words;
+       w += stride) {
+    int c = (int)(w & (uint64_t)(rstride - 1));
+    acc[first * (uint64_t)rstride + w] = c < nvals ? inits[c] : 0.0;
+  }
+}
+extern "C" int qk_groupby_dense_init(void *stream, double *acc, uint64_t first,
+                                     uint64_t count, int rstride, int nvals,
+                                     const double *inits_dev) {
+  if (!count) return 0;
+  if (nvals < 0 || rstride < 1 || rstride < nvals ||
+      !qk_pow2((uint64_t)rstride))
+    return qk_fail("qk_groupby_dense_init.rstride", hipErrorInvalidValue);
+  hipLaunchKernelGGL(k_groupby_dense_init,
+                     dim3(qk_grid(count * (uint64_t)rstride)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, first, count, rstride, nvals,
+                     inits_dev, acc);
+  QK_TRY("qk_groupby_dense_init", hipGetLastError());
+  return 0;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_groupby_dense_acc(
+    uint64_t n, const uint32_t *__restrict__ codes, uint32_t ncodes,
+    const double *const *__restrict__ vals,
+    const int32_t *__restrict__ agg_ops, int nvals, int rstride, double *acc,
+    uint32_t *err) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    uint32_t code = codes[i];
+    if (code >= ncodes) {  // never written past the records the host sized
+      atomicOr(err, 4u);
+      continue;
+    }
+    double *rec = acc + (uint64_t)code * (uint64_t)rstride;
+    for (int c = 0; c < nvals; c++) {
+      double v = vals[c][i];
+      int op = agg_ops ? agg_ops[c] : 0;
+      if (op == 1)
+        atomic_min_f64(&rec[c], v);
+      else if (op == 2)
+        atomic_max_f64(&rec[c], v);
+      else
+        atomicAdd(&rec[c], v);
+    }
+  }
+}
+extern "C" int qk_groupby_dense_acc(void *stream, uint64_t n,
+                                    const uint32_t *codes, uint32_t ncodes,
+                                    const void *vals_dev,
+                                    const int32_t *agg_ops_dev, int nvals,
+                                    int rstride, double *acc,
+                                    uint32_t *err_dev) {
+  if (!n || !nvals) return 0;
+  if (nvals < 0 || rstride < nvals || !qk_pow2((uint64_t)rstride))
+    return qk_fail("qk_groupby_dense_acc.rstride", hipErrorInvalidValue);
+  hipLaunchKernelGGL(k_groupby_dense_acc, dim3(qk_grid(n)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, n, codes, ncodes,
+                     (const double *const *)vals_dev, agg_ops_dev, nvals,
+                     rstride, acc, err_dev);
+  QK_TRY("qk_groupby_dense_acc", hipGetLastError());
+  return 0;
+}
+
 // ---- LIKE over free-text string columns --------------------------------
 // filter_sql("o_comment not like '%special%requests%'") and its kin
 // (apps/tpc-h/tpch.py:137,316,380,413,416,481) run inside DuckDB/polars in

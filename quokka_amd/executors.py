@@ -309,6 +309,140 @@ _AGG_RE = re.compile(r"(sum|min|max)\s*\(\s*([A-Za-z_][A-Za-z0-9_]*)\s*\)",
                      re.I)
 _AGG_OP = {"sum": 0, "min": 1, "max": 2}
 
+_CANON_NAN = np.float64(np.nan)
+
+
+def key_to_words(arr):
+    """Host numpy key column -> np.int64 words, one per row, such that two
+    rows hold equal words exactly when SQL puts them in one group:
+    bool and signed/unsigned ints are widened (uint64 keeps its bit
+    pattern), datetime64/timedelta64 give their integer count, floats give
+    the float64 bit pattern with -0.0 turned into +0.0 and every NaN into
+    one canonical NaN. words_to_key is the inverse."""
+    arr = np.asarray(arr)
+    kind = arr.dtype.kind
+    if kind == "b":
+        return arr.astype(np.int64)
+    if kind == "i":
+        return arr.astype(np.int64)
+    if kind == "u":
+        if arr.dtype.itemsize == 8:
+            return np.ascontiguousarray(arr).view(np.int64)
+        return arr.astype(np.int64)
+    if kind in "mM":
+        return np.ascontiguousarray(arr).view(np.int64)
+    if kind == "f":
+        f = arr.astype(np.float64)              # a copy
+        f[np.isnan(f)] = _CANON_NAN
+        f += 0.0                                # -0.0 + 0.0 == +0.0
+        return f.view(np.int64)
+    raise TypeError("key_to_words: unsupported key dtype %s" % arr.dtype)
+
+
+def words_to_key(words, dtype):
+    """Inverse of key_to_words for a column of numpy dtype `dtype` (a
+    float32 column comes back as float32, exactly)."""
+    words = np.ascontiguousarray(words, dtype=np.int64)
+    dtype = np.dtype(dtype)
+    kind = dtype.kind
+    if kind == "b":
+        return words != 0
+    if kind == "i":
+        return words.astype(dtype)
+    if kind == "u":
+        if dtype.itemsize == 8:
+            return words.view(np.uint64)
+        return words.astype(dtype)
+    if kind in "mM":
+        return words.view(dtype)
+    if kind == "f":
+        return words.view(np.float64).astype(dtype)
+    raise TypeError("words_to_key: unsupported key dtype %s" % dtype)
+
+
+class _KeyWords:
+    """Per-executor state that turns the key columns of a batch into
+    64-bit words (one np.int64 array per key) and back: the Arrow type of
+    each key from the first batch, and one DeviceStringDict per string
+    key. Numeric, bool and date/time keys convert on the host through
+    key_to_words; a string key's word is its dictionary code."""
+
+    def __init__(self, names):
+        self.names = list(names)
+        self.types = {}
+        self.dicts = {}
+
+    @staticmethod
+    def _storage(col):
+        """Arrow key column -> numpy array key_to_words accepts."""
+        import pyarrow as pa
+        if isinstance(col, pa.ChunkedArray):
+            col = col.combine_chunks()
+        t = col.type
+        if pa.types.is_dictionary(t):
+            col = col.dictionary_decode() if hasattr(col, "dictionary_decode") \
+                else col.cast(t.value_type)
+            t = col.type
+        if pa.types.is_date32(t) or pa.types.is_time32(t):
+            return col.cast(pa.int32()).to_numpy(zero_copy_only=False)
+        if pa.types.is_temporal(t):
+            return col.cast(pa.int64()).to_numpy(zero_copy_only=False)
+        if pa.types.is_boolean(t) or pa.types.is_integer(t) or \
+                pa.types.is_floating(t):
+            return col.to_numpy(zero_copy_only=False)
+        raise TypeError("unsupported group key type %s" % t)
+
+    def check(self, batch, who):
+        """Host-only: refuse null keys before any device work."""
+        for k in self.names:
+            if batch.column(k).null_count:
+                raise TypeError(
+                    "%s: key column %r has nulls; null keys are not "
+                    "supported (DESIGN.md §3a')" % (who, k))
+
+    def words(self, batch, ops):
+        outs = []
+        for k in self.names:
+            col = batch.column(k)
+            self.types.setdefault(k, col.type)
+            if _is_stringish(col):
+                sd = self.dicts.get(k)
+                if sd is None:
+                    sd = self.dicts[k] = ops.DeviceStringDict(expected=4096)
+                outs.append(sd.encode_column(col).astype(np.int64))
+            else:
+                outs.append(key_to_words(self._storage(col)))
+        return outs
+
+    def decode(self, name, words):
+        """words -> numpy values that sort like the column (strings as an
+        object array, dates as their integer count)."""
+        import pyarrow as pa
+        t = self.types[name]
+        sd = self.dicts.get(name)
+        if sd is not None:
+            return sd.decode(words)
+        if pa.types.is_date32(t) or pa.types.is_time32(t):
+            return words_to_key(words, np.int32)
+        if pa.types.is_temporal(t):
+            return words_to_key(words, np.int64)
+        return words_to_key(words, t.to_pandas_dtype())
+
+    def to_arrow(self, name, values):
+        """decode()'s values -> Arrow array of the key's original type."""
+        import pyarrow as pa
+        t = self.types[name]
+        if pa.types.is_dictionary(t):
+            t = t.value_type
+        if name in self.dicts:
+            return pa.array(values, type=t)
+        return pa.array(values).cast(t)
+
+    def free(self):
+        for sd in self.dicts.values():
+            sd.free()
+        self.dicts = {}
+
 
 class GPUAggExecutor(Executor):
     """GPU replacement for SQLAggExecutor (sql_executors.py:556-599).
@@ -324,15 +458,25 @@ class GPUAggExecutor(Executor):
     (single i64 group key, or multiple keys composite-encoded — DESIGN.md);
     done() extracts groups, evaluates the final expressions host-side over
     the per-group sums (tiny), applies order-by, returns a pyarrow Table.
+
+    device_keys=True lifts the limits of the composite encoding (at most 3
+    keys, 2**21 distinct values each): every key column becomes one 64-bit
+    word per row (key_to_words; strings by device dictionary code) and the
+    word tuples are grouped on the device (ops.GroupByKeys, DESIGN.md
+    §3a''): any number of keys, int / bool / date / float / string, up to
+    2**31 - 1 groups, key columns returned in their original Arrow types.
+    Null keys raise TypeError. The default is the composite path, as before.
     """
 
-    def __init__(self, groupby_keys, orderby_keys, sql_statement):
+    def __init__(self, groupby_keys, orderby_keys, sql_statement,
+                 device_keys=False):
         if not isinstance(groupby_keys, list):
             raise TypeError("groupby_keys must be a list (may be empty "
                             "for a grand aggregate)")
         self.groupby_keys = groupby_keys
         self.orderby_keys = orderby_keys or []
         self.sql_statement = sql_statement
+        self.device_keys = bool(device_keys)
         self.sum_cols = []          # partial columns referenced by aggs
         self.agg_ops = []           # per column: 0 SUM / 1 MIN / 2 MAX
         self.exprs = []             # (alias, python expr over s['col'])
@@ -373,6 +517,7 @@ class GPUAggExecutor(Executor):
             self.exprs.append((alias or part.strip(), expr))
         self._gb = None
         self._key_state = None
+        self._key_words = None      # _KeyWords of the device_keys path
 
     @staticmethod
     def _split_top(s):
@@ -480,6 +625,8 @@ class GPUAggExecutor(Executor):
         if not batches:
             return
         batch = pa.concat_tables(batches)
+        if self.device_keys and self.groupby_keys:
+            return self._execute_device_keys(batch)
         if self.groupby_keys:
             keys = self._encode_keys(batch)
         else:
@@ -497,9 +644,77 @@ class GPUAggExecutor(Executor):
         for v in vcols:
             v.free()
 
+    def _execute_device_keys(self, batch):
+        """device_keys=True: every key column becomes one 64-bit word per
+        row, the tuple of words one dense code (ops.GroupByKeys). Any
+        number of keys, any cardinality up to 2**31 - 1 groups."""
+        ops, shim, staging = _lazy_gpu()
+        if self._key_words is None:
+            self._key_words = _KeyWords(self.groupby_keys)
+        self._key_words.check(batch, type(self).__name__)
+        words = self._key_words.words(batch, ops)
+        if self._gb is None:
+            self._gb = ops.GroupByKeys(
+                len(self.groupby_keys), len(self.sum_cols),
+                agg_ops=self.agg_ops,
+                expected_groups=max(1024, len(batch)))
+        kcols = [shim.DevColumn.from_numpy(w) for w in words]
+        vcols = [shim.DevColumn.from_numpy(
+            staging.column_to_numpy(batch.column(c)).astype(np.float64))
+            for c in self.sum_cols]
+        try:
+            self._gb.update(kcols, vcols, len(batch))
+        finally:
+            for c in kcols + vcols:
+                c.free()
+
+    def _done_device_keys(self):
+        key_words, sums = self._gb.extract()
+        s = {c: sums[i] for i, c in enumerate(self.sum_cols)}
+        kw = self._key_words
+        out = {k: kw.decode(k, w)
+               for k, w in zip(self.groupby_keys, key_words)}
+        for alias, expr in self.exprs:
+            out[alias] = eval(expr, {"s": s})  # noqa: S307 — expr built above
+        # bool keys order as 0/1 (numpy refuses to negate a bool array)
+        order = self._order_by({k: (v.astype(np.uint8)
+                                    if getattr(v, "dtype", None) == np.bool_
+                                    else v) for k, v in out.items()})
+        if order is not None:
+            out = {k: np.asarray(v)[order] for k, v in out.items()}
+        for k in self.groupby_keys:
+            out[k] = kw.to_arrow(k, out[k])
+        self._gb.free()
+        self._gb = None
+        kw.free()
+        self._key_words = None
+        return _to_table(out)
+
+    def _order_by(self, out):
+        """Row order of the order-by clause over the output columns, or
+        None without one."""
+        if not self.orderby_keys:
+            return None
+        cols = []
+        for item in reversed(self.orderby_keys):
+            k, d = item if isinstance(item, (tuple, list)) else (item, "asc")
+            v = np.asarray(out[k])
+            if d == "desc":
+                if v.dtype.kind in "biuf":
+                    v = -v
+                else:
+                    # non-numeric desc (e.g. decoded string group keys):
+                    # invert factorized rank instead of numeric negation
+                    _, inv = np.unique(v, return_inverse=True)
+                    v = inv.max() - inv
+            cols.append(v)
+        return np.lexsort(cols)
+
     def done(self, executor_id):
         if self._gb is None:
             return None
+        if self.device_keys and self.groupby_keys:
+            return self._done_device_keys()
         keys, sums = self._gb.extract()
         s = {c: sums[i] for i, c in enumerate(self.sum_cols)}
         out = {}
@@ -512,21 +727,8 @@ class GPUAggExecutor(Executor):
                                              else keys)
         for alias, expr in self.exprs:
             out[alias] = eval(expr, {"s": s})  # noqa: S307 — expr built above
-        if self.orderby_keys:
-            cols = []
-            for item in reversed(self.orderby_keys):
-                k, d = item if isinstance(item, (tuple, list)) else (item, "asc")
-                v = np.asarray(out[k])
-                if d == "desc":
-                    if v.dtype.kind in "biuf":
-                        v = -v
-                    else:
-                        # non-numeric desc (e.g. decoded string group keys):
-                        # invert factorized rank instead of numeric negation
-                        _, inv = np.unique(v, return_inverse=True)
-                        v = inv.max() - inv
-                cols.append(v)
-            order = np.lexsort(cols)
+        order = self._order_by(out)
+        if order is not None:
             out = {k: np.asarray(v)[order] for k, v in out.items()}
         self._gb.free()
         self._gb = None
@@ -721,19 +923,59 @@ class GPUDistinctExecutor(Executor):
     """= DistinctExecutor (sql_executors.py:517-554): per batch, emit the
     rows whose key was never seen before (batch.unique() then anti-join
     against the accumulated state, :529-543). Device hash table keyed i64;
-    done() returns None like the reference (state already emitted)."""
+    done() returns None like the reference (state already emitted).
+
+    `keys` as a str or a one-element list is that single-column path. A
+    list of two or more columns is the reference's unique(subset=keys)
+    over all of them, through ops.DeviceKeyDict (DESIGN.md §3a'')."""
 
     def __init__(self, keys):
-        self.keys = keys if isinstance(keys, str) else keys[0]
-        if not isinstance(self.keys, str):
-            raise TypeError("single distinct key column expected")
+        self._multi = not isinstance(keys, str) and len(keys) >= 2
+        if self._multi:
+            # unique(subset=keys) over two or more columns: every row's
+            # key tuple -> one dense code (ops.DeviceKeyDict)
+            self.keys = list(keys)
+            if not all(isinstance(k, str) for k in self.keys):
+                raise TypeError("distinct key column names expected")
+        else:
+            self.keys = keys if isinstance(keys, str) else keys[0]
+            if not isinstance(self.keys, str):
+                raise TypeError("single distinct key column expected")
         self._table = None
         self._n_rows = 0
         self._key_dict = None       # DeviceStringDict for string keys
+        self._kd = None             # DeviceKeyDict of the multi-key path
+        self._key_words = None
 
     def __getstate__(self):
-        assert self._table is None, "pickle before first execute"
+        assert self._table is None and self._kd is None, \
+            "pickle before first execute"
         return dict(self.__dict__)
+
+    def _execute_multi(self, batch):
+        """Emit the rows whose key tuple no earlier batch held and that
+        are the first of this batch with it: code >= the code count before
+        the batch, first occurrence of that code."""
+        ops, shim, staging = _lazy_gpu()
+        if self._key_words is None:
+            self._key_words = _KeyWords(self.keys)
+        self._key_words.check(batch, type(self).__name__)
+        words = self._key_words.words(batch, ops)
+        if self._kd is None:
+            self._kd = ops.DeviceKeyDict(len(self.keys),
+                                         expected=max(1024, len(batch)))
+        before = self._kd.n_codes
+        kcols = [shim.DevColumn.from_numpy(w) for w in words]
+        try:
+            dcodes = self._kd.encode(kcols, len(batch))
+        finally:
+            for c in kcols:
+                c.free()
+        codes = dcodes.to_numpy(len(batch))
+        dcodes.free()
+        ucodes, first_idx = np.unique(codes, return_index=True)
+        sel = np.sort(first_idx[ucodes >= before])
+        return batch.take(sel) if len(sel) else None
 
     def execute(self, batches, stream_id, executor_id):
         import pyarrow as pa
@@ -742,6 +984,8 @@ class GPUDistinctExecutor(Executor):
         if not batches:
             return
         batch = pa.concat_tables(batches)
+        if self._multi:
+            return self._execute_multi(batch)
         key_col = batch.column(self.keys)
         if _is_stringish(key_col):
             # device string dictionary -> dense codes (consistent across

@@ -522,6 +522,263 @@ class DeviceStringDict:
         self._ctr.free()
 
 
+def _dev_ptr_array(cols):
+    """Device array of the columns' pointers (the `T *const *` argument of
+    the multi-column kernels). Caller frees."""
+    ptrs = np.array([c.ptr.value if hasattr(c.ptr, "value") else c.ptr
+                     for c in cols], dtype=np.uint64)
+    buf = DevBuffer(ptrs.nbytes)
+    shim.call("qk_h2d", buf.ptr, ptrs.ctypes.data_as(c_vp),
+              c_u64(ptrs.nbytes))
+    return buf
+
+
+class DeviceKeyDict:
+    """Device dictionary over K full-width key columns: each row's tuple
+    of K 64-bit words -> a dense u32 code, the same in every later batch
+    (slot array, key store and counter persist; growth re-seats the slots
+    and copies the store, codes never change). What DeviceStringDict is
+    for one string column, for the arbitrary groupby_keys / subset lists
+    of SQLAggExecutor and DistinctExecutor (sql_executors.py:556-599,
+    :517-554). No key value is reserved; growth is internal."""
+
+    MAX_CODES = 2 ** 31 - 1
+
+    def __init__(self, nkeys, expected=1024, stream=None):
+        if int(nkeys) < 1:
+            raise ValueError("DeviceKeyDict: nkeys must be >= 1")
+        self.nkeys = int(nkeys)
+        self.stream = stream
+        self.cap = _pow2_at_least(max(2, 2 * int(expected)))
+        self.slots = self._new_slots(self.cap)
+        self.code_cap = max(1, int(expected))
+        self.store = DevColumn(np.int64, self.nkeys * self.code_cap)
+        self._ctr = DevBuffer(8)            # [counter u32, error u32]
+        shim.call("qk_dmemset", self._ctr.ptr, 0, c_u64(8))
+        self.n_codes = 0
+        self._broken = False
+
+    @staticmethod
+    def _new_slots(cap):
+        s = DevColumn(np.uint64, cap)
+        shim.call("qk_dmemset", s.ptr, 0, c_u64(cap * 8))
+        return s
+
+    @property
+    def _err_ptr(self):
+        return shim.c_vp(self._ctr.ptr.value + 4)
+
+    def _sync_state(self, sh, what):
+        shim.call("qk_stream_sync", sh)
+        host = np.zeros(2, dtype=np.uint32)
+        shim.call("qk_d2h", host.ctypes.data_as(c_vp), self._ctr.ptr,
+                  c_u64(8))
+        if host[1]:
+            self._broken = True
+            raise RuntimeError(
+                "DeviceKeyDict.%s: device error word %d (1 = probe walk "
+                "exhausted the slot array, 2 = key store full); the "
+                "dictionary is unusable" % (what, int(host[1])))
+        self.n_codes = int(host[0])
+
+    def _ensure(self, n, sh):
+        need = self.n_codes + n
+        if need > self.MAX_CODES:
+            raise ValueError(
+                "DeviceKeyDict: %d codes + %d rows exceeds the limit of "
+                "2**31 - 1 groups" % (self.n_codes, n))
+        if need > self.code_cap:
+            new_cc = _pow2_at_least(2 * need)
+            new = DevColumn(np.int64, self.nkeys * new_cc)
+            shim.call("qk_stream_sync", sh)
+            if self.n_codes:
+                for k in range(self.nkeys):
+                    shim.call(
+                        "qk_d2d", shim.c_vp(new.ptr.value + k * new_cc * 8),
+                        shim.c_vp(self.store.ptr.value
+                                  + k * self.code_cap * 8),
+                        c_u64(self.n_codes * 8))
+            # the old store may be recycled by the pool: copies first
+            shim.call("qk_stream_sync", None)
+            self.store.free()
+            self.store = new
+            self.code_cap = new_cc
+        if 2 * need > self.cap:
+            self.slots.free()
+            self.cap = _pow2_at_least(2 * need)
+            self.slots = self._new_slots(self.cap)
+            shim.call("qk_keydict_rehash", sh, c_u32(self.n_codes),
+                      self.nkeys, self.store.ptr, c_u64(self.code_cap),
+                      self.slots.ptr, c_u64(self.cap), self._err_ptr)
+            self._sync_state(sh, "rehash")
+
+    def encode(self, key_cols, n=None):
+        """key_cols: K int64 DevColumns (one 64-bit word per row and key).
+        Returns a DevColumn of u32 codes, n rows; caller frees."""
+        if self._broken:
+            raise RuntimeError("DeviceKeyDict: unusable after a device "
+                               "error")
+        if len(key_cols) != self.nkeys:
+            raise ValueError("DeviceKeyDict.encode: %d key columns, "
+                             "expected %d" % (len(key_cols), self.nkeys))
+        for c in key_cols:
+            if c.dtype != np.dtype(np.int64):
+                raise TypeError("DeviceKeyDict.encode: key columns are "
+                                "int64 words, got %s" % c.dtype)
+        n = min(c.n for c in key_cols) if n is None else int(n)
+        if any(c.n < n for c in key_cols):
+            raise ValueError("DeviceKeyDict.encode: a key column is "
+                             "shorter than n")
+        if n >= 2 ** 32:
+            raise ValueError("DeviceKeyDict.encode: at most 2**32 - 1 rows "
+                             "per call")
+        out = DevColumn(np.uint32, n)
+        if not n:
+            return out
+        sh = self.stream.handle if self.stream else None
+        self._ensure(n, sh)
+        dptrs = _dev_ptr_array(key_cols)
+        row_slot = DevColumn(np.uint64, n)
+        shim.call("qk_keydict_encode", sh, c_u64(n), self.nkeys, dptrs.ptr,
+                  self.slots.ptr, c_u64(self.cap), self.store.ptr,
+                  c_u64(self.code_cap), self._ctr.ptr, row_slot.ptr,
+                  out.ptr, self._err_ptr)
+        try:
+            self._sync_state(sh, "encode")
+        finally:
+            dptrs.free()
+            row_slot.free()
+        return out
+
+    def keys_host(self):
+        """-> list of K np.int64 arrays of n_codes words, index == code."""
+        outs = []
+        for k in range(self.nkeys):
+            a = np.empty(self.n_codes, dtype=np.int64)
+            if self.n_codes:
+                shim._bounce.d2h(a, shim.c_vp(
+                    self.store.ptr.value + k * self.code_cap * 8))
+            outs.append(a)
+        return outs
+
+    def free(self):
+        self.slots.free()
+        self.store.free()
+        self._ctr.free()
+
+
+class GroupByKeys:
+    """Group-by over K full-width key columns with nvals f64 SUM/MIN/MAX
+    columns: DeviceKeyDict codes, then one dense accumulate into the
+    record of each row's code (SQLAggExecutor's DuckDB group-by over an
+    arbitrary groupby_keys list, sql_executors.py:556-599). Because codes
+    are dense the accumulate needs no second hash walk and extract() no
+    compaction. Growth is internal; the group limit is 2**31 - 1."""
+
+    AGG_INIT = GroupByI64.AGG_INIT
+
+    def __init__(self, nkeys, nvals, agg_ops=None, expected_groups=1024,
+                 stream=None):
+        self.nvals = int(nvals)
+        self.agg_ops = list(agg_ops) if agg_ops else [0] * self.nvals
+        assert len(self.agg_ops) == self.nvals
+        self.stream = stream
+        self.dict = DeviceKeyDict(nkeys, expected_groups, stream)
+        self.rstride = _pow2_at_least(max(1, self.nvals))
+        self._inits_dev = DevColumn.from_numpy(
+            np.asarray([self.AGG_INIT[op] for op in self.agg_ops] or [0.0],
+                       dtype=np.float64))
+        self._ops_dev = None
+        if any(self.agg_ops):
+            self._ops_dev = DevColumn.from_numpy(
+                np.asarray(self.agg_ops, dtype=np.int32))
+        self._err = DevBuffer(4)
+        shim.call("qk_dmemset", self._err.ptr, 0, c_u64(4))
+        self.acc_cap = max(1, int(expected_groups))
+        self.acc = DevColumn(np.float64, self.acc_cap * self.rstride)
+        self._init_records(self.acc, 0, self.acc_cap)
+
+    @property
+    def n_groups(self):
+        return self.dict.n_codes
+
+    def _init_records(self, acc, first, count):
+        sh = self.stream.handle if self.stream else None
+        shim.call("qk_groupby_dense_init", sh, acc.ptr, c_u64(first),
+                  c_u64(count), self.rstride, self.nvals,
+                  self._inits_dev.ptr)
+
+    def _grow_acc(self, need):
+        """Records of existing codes move by device copy; the new capacity
+        starts at the op identities."""
+        new_cap = _pow2_at_least(2 * need)
+        new = DevColumn(np.float64, new_cap * self.rstride)
+        sh = self.stream.handle if self.stream else None
+        shim.call("qk_stream_sync", sh)
+        shim.call("qk_d2d", new.ptr, self.acc.ptr,
+                  c_u64(self.acc_cap * self.rstride * 8))
+        self._init_records(new, self.acc_cap, new_cap - self.acc_cap)
+        shim.call("qk_stream_sync", sh)
+        self.acc.free()
+        self.acc = new
+        self.acc_cap = new_cap
+
+    def update(self, key_cols, val_cols, n=None):
+        assert len(val_cols) == self.nvals
+        n = min(c.n for c in key_cols) if n is None else int(n)
+        if not n:
+            return
+        for v in val_cols:
+            if v.dtype != np.dtype(np.float64) or v.n < n:
+                raise TypeError("GroupByKeys.update: value columns are "
+                                "float64 with at least n rows")
+        codes = self.dict.encode(key_cols, n)
+        try:
+            if not self.nvals:
+                return
+            if self.dict.n_codes > self.acc_cap:
+                self._grow_acc(self.dict.n_codes)
+            sh = self.stream.handle if self.stream else None
+            dptrs = _dev_ptr_array(val_cols)
+            shim.call("qk_groupby_dense_acc", sh, c_u64(n), codes.ptr,
+                      c_u32(self.dict.n_codes), dptrs.ptr,
+                      self._ops_dev.ptr if self._ops_dev else None,
+                      self.nvals, self.rstride, self.acc.ptr, self._err.ptr)
+            shim.call("qk_stream_sync", sh)
+            dptrs.free()
+            err = np.zeros(1, dtype=np.uint32)
+            shim.call("qk_d2h", err.ctypes.data_as(c_vp), self._err.ptr,
+                      c_u64(4))
+            if err[0]:
+                raise RuntimeError("GroupByKeys.update: a code lay beyond "
+                                   "the accumulator records (device error "
+                                   "word %d)" % int(err[0]))
+        finally:
+            codes.free()
+
+    def extract(self):
+        """-> (list of K np.int64 key-word arrays [G], sums np.float64
+        [nvals, G]); row g of every array belongs to code g."""
+        g = self.dict.n_codes
+        keys = self.dict.keys_host()
+        recs = np.empty(g * self.rstride, dtype=np.float64)
+        if g and self.nvals:
+            shim.call("qk_stream_sync",
+                      self.stream.handle if self.stream else None)
+            shim._bounce.d2h(recs, self.acc.ptr)
+        sums = np.ascontiguousarray(
+            recs.reshape(g, self.rstride)[:, :self.nvals].T)
+        return keys, sums
+
+    def free(self):
+        self.dict.free()
+        self.acc.free()
+        self._inits_dev.free()
+        self._err.free()
+        if self._ops_dev is not None:
+            self._ops_dev.free()
+
+
 class StringColumn:
     """Device-resident Arrow string column: `offsets` (DevColumn i32 or
     i64, n+1 entries starting at 0) + `data` (DevBuffer of the string

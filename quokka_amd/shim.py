@@ -144,6 +144,14 @@ _SIGS = {
                            c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "qk_str_dict_rehash": [c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp,
                            c_u64],
+    "qk_keydict_encode": [c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_u64,
+                          c_vp, c_u64, c_vp, c_vp, c_vp, c_vp],
+    "qk_keydict_rehash": [c_vp, c_u32, ctypes.c_int, c_vp, c_u64, c_vp,
+                          c_u64, c_vp],
+    "qk_groupby_dense_init": [c_vp, c_vp, c_u64, c_u64, ctypes.c_int,
+                              ctypes.c_int, c_vp],
+    "qk_groupby_dense_acc": [c_vp, c_u64, c_vp, c_u32, c_vp, c_vp,
+                             ctypes.c_int, ctypes.c_int, c_vp, c_vp],
     "qk_str_like_i32": [c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.c_int, c_vp],
     "qk_str_like_i64": [c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.c_int, c_vp],
     "qk_str_like_path_i32": [c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.c_int,
