@@ -741,19 +741,6 @@ int qk_pq_walk_pages(const uint8_t *buf, uint64_t start,
                      uint64_t total_len, int64_t num_values, int64_t *out,
                      int64_t max_pages, int64_t *n_out);
 
-/* ---- GPU CSV parse ---------------------------------------------------- *
- * The reference's CSV scan splits files into byte ranges and decodes on
- * the CPU with polars.read_csv (unordered_readers.py:273-442, :438).
- * Here the raw bytes live in HBM: qk_csv_newlines builds the ORDERED
- * newline index (u64 positions; count written to out_count_dev), then
- * qk_csv_parse decodes one row per thread. coltypes: 0=i64, 1=f64
- * (decimal, <=15 significant digits — parsed as exact-int / exact
- * power-of-ten division, BIT-EXACT vs strtod; more digits = row error),
- * 2=date32 ("YYYY-MM-DD" -> days since epoch), 3=u8 dictionary code
- * (candidates as first-8-bytes-LE u64 + length, <=32 per column,
- * unknown value = row error), 4=skip. Trailing '\r' stripped; trailing
- * separators (dbgen .tbl) tolerated. err_row: device u64 initialized to
- * UINT64_MAX; the LOWEST failing row index lands there. */
 /* Range-partition ids (quokka_runtime.py:234-243 partition_key_range):
  * id = (key - 1) / (total_range / nparts), floor division, clamped into
  * [0, nparts-1] (the reference misroutes keys outside [1, total_range];
@@ -764,6 +751,44 @@ int qk_pq_walk_pages(const uint8_t *buf, uint64_t start,
 int qk_range_part_ids(void *stream, uint64_t n, const int64_t *keys,
                       int64_t per_range, uint32_t nparts, int64_t *out);
 
+/* ---- GPU CSV parse ---------------------------------------------------- *
+ * The reference's CSV scan splits files into byte ranges and decodes on
+ * the CPU with polars.read_csv (unordered_readers.py:273-442, :438).
+ * Here the raw bytes live in HBM: qk_csv_newlines builds the ORDERED
+ * newline index (u64 positions; count written to out_count_dev), then
+ * qk_csv_parse decodes one row per thread. Anything unparseable is a row
+ * error, never a silently different value. coltypes:
+ *  0=i64: [+-]digits, at most 18 digits.
+ *  1=f64: [+-]digits[.digits] with at least one digit, <=15 significant
+ *    digits and <=18 decimals — parsed as exact-int / exact power-of-ten
+ *    division, BIT-EXACT vs strtod ("-0" is -0.0).
+ *  2=date32: exactly "YYYY-MM-DD", a real day of the proleptic Gregorian
+ *    calendar (day checked against month and leap rule) -> days since
+ *    1970-01-01.
+ *  3=u8 dictionary code: the field must equal a candidate byte for byte
+ *    over its whole length; unknown value = row error. <=32 candidates
+ *    per column. dict_cands/dict_lens (first 8 bytes LE, length clamped
+ *    to 255) are the prefilter; dict_bytes holds all candidates' bytes
+ *    back to back and dict_offs[ncols * QK_CSV_MAX_DICT + 1] their u32
+ *    start offsets (slot c * QK_CSV_MAX_DICT + j runs to the next slot's
+ *    offset; unused slots are empty), against which a hit is confirmed.
+ *  4=skip: any bytes.
+ * Rows: a trailing '\r' is stripped (a '\r' elsewhere is field data);
+ * exactly one trailing separator after the last schema field (dbgen
+ * .tbl) is tolerated; fewer fields than the schema, or any further field
+ * after it — an empty one included — is a row error. A field that starts
+ * with quote_char runs to its closing quote ("" escapes stay in the
+ * slice, so they fail typed parses); a missing closing quote, or a byte
+ * other than the separator or the row end after it, is a row error.
+ * Where this is stricter or more lenient than strtod / pyarrow.csv:
+ * STRICTER — no exponent, inf, nan, hex or surrounding blanks; f64 text
+ * with >15 significant digits or >18 decimals and i64 text with >18
+ * digits are errors although strtod / strtoll can read them (the parse
+ * would no longer be exact); empty fields are errors, not nulls, except
+ * for an empty dictionary candidate. MORE LENIENT — year 0000 is read
+ * as the proleptic year 0.
+ * err_row: device u64 initialized to UINT64_MAX; the LOWEST failing row
+ * index lands there. */
 #define QK_CSV_MAX_DICT 32
 int qk_csv_newlines(void *stream, uint64_t data_start, uint64_t n,
                     const uint8_t *bytes, uint64_t *out_pos,
@@ -771,7 +796,9 @@ int qk_csv_newlines(void *stream, uint64_t data_start, uint64_t n,
 /* Quote-aware variant (RFC-4180): a newline ends a row only when the
  * count of `quote` chars before it is even ("" escapes toggle twice and
  * cancel). Slower 5-pass path; callers use it only when the buffer
- * contains the quote char at all. */
+ * contains the quote char at all. An odd total number of quote chars
+ * (a quote never closed, which would swallow every later row) writes
+ * UINT64_MAX to out_count_dev; out_pos is then unspecified. */
 int qk_csv_newlines_quoted(void *stream, uint64_t data_start, uint64_t n,
                            const uint8_t *bytes_dev, uint8_t quote_char,
                            uint64_t *out_pos_dev, uint64_t *out_count_dev);
@@ -780,7 +807,8 @@ int qk_csv_parse(void *stream, uint64_t nrows, const uint8_t *bytes,
                  uint8_t quote_char /* 0 = no quoting */, int ncols,
                  const int *coltypes, void *const *out_ptrs,
                  const uint64_t *dict_cands, const uint8_t *dict_lens,
-                 const int *ncands, uint64_t *err_row);
+                 const int *ncands, const uint8_t *dict_bytes,
+                 const uint32_t *dict_offs, uint64_t *err_row);
 
 #ifdef __cplusplus
 }

@@ -4284,6 +4284,10 @@ extern "C" int qk_csv_newlines(void *stream, uint64_t data_start, uint64_t n,
 // tiny prefix scan over per-unit quote counts between passes:
 //   1. quotes per unit   2. prefix parity   3. valid-\n count per unit
 //   4. k_scan_blocks exclusive offsets      5. scatter positions
+// An odd TOTAL quote count means a quote is never closed: every newline
+// after it would count as data and those rows would vanish. parity
+// [nblocks] keeps the total's parity and k_csv_flag_odd turns it into
+// the UINT64_MAX row count the header documents.
 __global__ void k_scan_parity(uint64_t nblocks, const uint64_t *counts,
                               uint8_t *parity) {
   uint64_t acc = 0;
@@ -4291,6 +4295,11 @@ __global__ void k_scan_parity(uint64_t nblocks, const uint64_t *counts,
     parity[i] = (uint8_t)(acc & 1);
     acc += counts[i];
   }
+  parity[nblocks] = (uint8_t)(acc & 1);
+}
+__global__ void k_csv_flag_odd(const uint8_t *total_parity,
+                               uint64_t *out_count) {
+  if (*total_parity) *out_count = ~0ull;
 }
 __global__ void __launch_bounds__(BLOCK) k_csv_quote_count_w(
     uint64_t lo0, uint64_t n, const uint8_t *__restrict__ b, uint64_t unit,
@@ -4384,6 +4393,8 @@ extern "C" int qk_csv_newlines_quoted(void *stream, uint64_t data_start,
   hipLaunchKernelGGL(k_csv_nl_scatter_qw, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, data_start, n, bytes, unit,
                      units, quote, par, scratch, out_pos);
+  hipLaunchKernelGGL(k_csv_flag_odd, dim3(1), dim3(1), 0,
+                     (hipStream_t)stream, par + units, out_count_dev);
   QK_TRY("qk_csv_newlines_quoted", hipGetLastError());
   return 0;
 }
@@ -4422,7 +4433,7 @@ __device__ inline bool csv_f64(const uint8_t *b, uint64_t s, uint64_t e,
   if (s >= e) return false;
   int64_t m = 0;
   int nd = 0, k = 0;
-  bool dot = false;
+  bool dot = false, digit = false;
   for (; s < e; s++) {
     uint8_t c = b[s];
     if (c == '.') {
@@ -4432,11 +4443,13 @@ __device__ inline bool csv_f64(const uint8_t *b, uint64_t s, uint64_t e,
     }
     c -= '0';
     if (c > 9) return false;
+    digit = true;
     if (nd || c) nd++;                    // significant digits
     m = m * 10 + c;
     if (dot) k++;
     if (nd > 15 || k > 18) return false;  // beyond bit-exact range
   }
+  if (!digit) return false;               // ".", "+.", "-." (strtod: no)
   double v = (double)m / P10[k];
   *out = neg ? -v : v;
   return true;
@@ -4460,7 +4473,11 @@ __device__ inline bool csv_date32(const uint8_t *b, uint64_t s, uint64_t e,
     if (c > 9) return false;
     d = d * 10 + c;
   }
-  if (mo < 1 || mo > 12 || d < 1 || d > 31) return false;
+  if (mo < 1 || mo > 12 || d < 1) return false;
+  // days in the month, proleptic Gregorian leap rule
+  bool leap = (y % 4 == 0) && (y % 100 != 0 || y % 400 == 0);
+  int dim = mo == 2 ? (leap ? 29 : 28) : 30 + ((mo + (mo >> 3)) & 1);
+  if (d > dim) return false;
   // Howard Hinnant days_from_civil (public-domain algorithm)
   int yy = y - (mo <= 2);
   int era = (yy >= 0 ? yy : yy - 399) / 400;
@@ -4480,6 +4497,8 @@ __global__ void __launch_bounds__(BLOCK) k_csv_parse(
     const int *__restrict__ coltypes, void *const *__restrict__ outs,
     const uint64_t *__restrict__ dict_cands,
     const uint8_t *__restrict__ dict_lens, const int *__restrict__ ncands,
+    const uint8_t *__restrict__ dict_bytes,
+    const uint32_t *__restrict__ dict_offs,
     unsigned long long *__restrict__ err_row) {
   uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -4488,7 +4507,9 @@ __global__ void __launch_bounds__(BLOCK) k_csv_parse(
     uint64_t row_end = nl[r];
     if (row_end > pos && b[row_end - 1] == '\r') row_end--;
     bool ok = true;
+    bool more = true;   // a field starts at pos (the first, or after a sep)
     for (int c = 0; c < ncols && ok; c++) {
+      if (!more) { ok = false; break; }  // fewer fields than the schema
       uint64_t fs = pos, fe;
       if (quote && pos < row_end && b[pos] == quote) {
         // RFC-4180 quoted field: content [pos+1, closing quote);
@@ -4504,12 +4525,18 @@ __global__ void __launch_bounds__(BLOCK) k_csv_parse(
             fe++;
           }
         }
-        uint64_t after = fe < row_end ? fe + 1 : row_end;
-        pos = (after < row_end && b[after] == sep) ? after + 1 : after;
+        // the closing quote must exist and be followed by the
+        // separator or the row end: '"12"9,5' is an error, not (12, 9)
+        if (fe >= row_end) { ok = false; break; }
+        uint64_t after = fe + 1;
+        more = after < row_end;
+        if (more && b[after] != sep) { ok = false; break; }
+        pos = more ? after + 1 : after;
       } else {
         fe = pos;
         while (fe < row_end && b[fe] != sep) fe++;
-        pos = fe < row_end ? fe + 1 : row_end;
+        more = fe < row_end;
+        pos = more ? fe + 1 : row_end;
       }
       switch (coltypes[c]) {
         case 0: ok = csv_i64(b, fs, fe, (int64_t *)outs[c] + r); break;
@@ -4520,14 +4547,22 @@ __global__ void __launch_bounds__(BLOCK) k_csv_parse(
           uint64_t w = 0;
           for (uint64_t i = 0; i < 8 && i < len; i++)
             w |= (uint64_t)b[fs + i] << (8 * i);
+          // (first 8 bytes, clamped length) is only the prefilter; a
+          // hit counts once the candidate's full length and every byte
+          // past the eighth agree. Each thread walks its own field:
+          // bounded by len, nothing shared across lanes.
           int code = -1;
-          for (int j = 0; j < ncands[c]; j++)
-            if (dict_cands[c * QK_CSV_MAX_DICT + j] == w &&
-                dict_lens[c * QK_CSV_MAX_DICT + j] ==
-                    (uint8_t)(len > 255 ? 255 : len)) {
-              code = j;
-              break;
-            }
+          for (int j = 0; j < ncands[c] && code < 0; j++) {
+            int slot = c * QK_CSV_MAX_DICT + j;
+            if (dict_cands[slot] != w ||
+                dict_lens[slot] != (uint8_t)(len > 255 ? 255 : len))
+              continue;
+            uint32_t off = dict_offs[slot];
+            if ((uint64_t)(dict_offs[slot + 1] - off) != len) continue;
+            uint64_t i = 8;
+            while (i < len && b[fs + i] == dict_bytes[off + i]) i++;
+            if (i >= len) code = j;
+          }
           if (code < 0) { ok = false; break; }
           ((uint8_t *)outs[c])[r] = (uint8_t)code;
           break;
@@ -4535,6 +4570,9 @@ __global__ void __launch_bounds__(BLOCK) k_csv_parse(
         default: break;                  // 4 = skip
       }
     }
+    // past the schema only one trailing separator may remain (pos sits
+    // just after it); anything else is a surplus field
+    if (ok && pos < row_end) ok = false;
     if (!ok) atomicMin(err_row, (unsigned long long)r);
   }
 }
@@ -4546,13 +4584,15 @@ extern "C" int qk_csv_parse(void *stream, uint64_t nrows,
                             const int *coltypes, void *const *out_ptrs,
                             const uint64_t *dict_cands,
                             const uint8_t *dict_lens, const int *ncands,
-                            uint64_t *err_row) {
+                            const uint8_t *dict_bytes,
+                            const uint32_t *dict_offs, uint64_t *err_row) {
   if (!nrows) return 0;
   uint32_t blocks = qk_grid(nrows);
   hipLaunchKernelGGL(k_csv_parse, dim3(blocks), dim3(BLOCK), 0,
                      (hipStream_t)stream, nrows, bytes, data_start, nl_pos,
                      sep, quote, ncols, coltypes, out_ptrs, dict_cands,
-                     dict_lens, ncands, (unsigned long long *)err_row);
+                     dict_lens, ncands, dict_bytes, dict_offs,
+                     (unsigned long long *)err_row);
   QK_TRY("qk_csv_parse", hipGetLastError());
   return 0;
 }

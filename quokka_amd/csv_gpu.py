@@ -9,10 +9,16 @@ field parsing there (include/quokka_amd.h for the exact contract).
 
 Schema entries: (name, "i64" | "f64" | "date" | "skip") or
 (name, "dict", [candidate strings]) — dict columns come back as u8 code
-columns (the executors' string-dict form), codes = candidate index.
+columns (the executors' string-dict form), codes = candidate index; a
+field matches a candidate only if it equals it byte for byte.
 Numeric parsing is bit-exact vs strtod for <= 15 significant digits;
 anything unparseable raises QkCsvError with the failing row, never a
-silently different value.
+silently different value. The exact accept/reject rules per type, and
+where they are stricter than strtod / pyarrow, are stated once, next to
+the qk_csv_parse prototype in include/quokka_amd.h. Row structure: a
+row must hold every schema field; one trailing separator after the last
+one (dbgen .tbl) is tolerated, any further field is an error (no in-tree
+caller passes a prefix schema; name the extra columns "skip").
 
 RFC-4180 quoting is supported (quote='"', the reference hands quoting to
 polars.read_csv): a field starting with the quote char runs to the
@@ -21,7 +27,10 @@ quotes escape. When the buffer contains no quote byte at all the
 original single-pass newline kernel runs unchanged; otherwise a
 parity-prefix pass validates newlines (qk_csv_newlines_quoted). Escaped
 "" inside numeric/dict fields still fail the parse (error, never wrong
-data) — same behaviour as the reference's typed readers.
+data) — same behaviour as the reference's typed readers. A closing quote
+must be followed by the separator or the row end, and a buffer with an
+odd number of quote bytes (a quote never closed, which would swallow the
+rows after it) raises QkCsvError.
 """
 import ctypes
 
@@ -48,10 +57,10 @@ def read_csv(source, schema, sep="|", header=False, quote='"'):
     """Decode a CSV byte buffer (or file path) into device columns.
 
     Returns dict name -> DevColumn (u8 codes for dict columns; the
-    candidate list you passed is the codebook). The buffer must end with
-    a newline on its final row (a trailing partial line is ignored, the
-    same contract as the reference's byte-range splitting
-    unordered_readers.py:372-383)."""
+    candidate list you passed is the codebook). A final row without a
+    newline is parsed like any other: the byte-range splitting that
+    drops partial lines (unordered_readers.py:372-383) is GPUCSVReader's
+    job and has happened before the buffer gets here."""
     from . import shim
     from .shim import DevBuffer, DevColumn, c_u64, c_vp
 
@@ -94,6 +103,11 @@ def read_csv(source, schema, sep="|", header=False, quote='"'):
     shim.call("qk_d2h", host_cnt.ctypes.data_as(c_vp), cnt.ptr, c_u64(8))
     nrows = int(host_cnt[0])
     cnt.free()
+    if nrows == np.iinfo(np.uint64).max:
+        pos.free()
+        dev.free()
+        raise QkCsvError("odd number of quote bytes %r: a quoted field is "
+                         "never closed" % quote)
     assert nrows <= n, (nrows, n)
     if nrows == 0:
         pos.free()
@@ -112,6 +126,8 @@ def read_csv(source, schema, sep="|", header=False, quote='"'):
     cands = np.zeros(ncols * MAX_DICT, dtype=np.uint64)
     clens = np.zeros(ncols * MAX_DICT, dtype=np.uint8)
     ncands = np.zeros(ncols, dtype=np.int32)
+    coffs = np.zeros(ncols * MAX_DICT + 1, dtype=np.uint32)
+    cbytes = []
     outs = {}
     out_ptrs = np.zeros(ncols, dtype=np.uint64)
     for c, spec in enumerate(schema):
@@ -124,25 +140,37 @@ def read_csv(source, schema, sep="|", header=False, quote='"'):
             if not 0 < len(values) <= MAX_DICT:
                 raise QkCsvError("dict column %r needs 1..%d candidates"
                                  % (name, MAX_DICT))
-            keys = [_dict_key(v) for v in values]
-            if len(set(keys)) != len(keys):
-                raise QkCsvError("dict column %r candidates collide in "
-                                 "(first 8 bytes, length)" % name)
-            for j, (w, ln) in enumerate(keys):
+            if len(set(values)) != len(values):
+                raise QkCsvError("dict column %r lists a candidate twice"
+                                 % name)
+            # (first 8 bytes, length) is the kernel's prefilter; the full
+            # bytes decide, so candidates may share a key
+            for j, v in enumerate(values):
+                w, ln = _dict_key(v)
                 cands[c * MAX_DICT + j] = w
                 clens[c * MAX_DICT + j] = ln
+                cbytes.append((c * MAX_DICT + j, v.encode()))
             ncands[c] = len(values)
         col = DevColumn(_OUT_DTYPE[coltypes[c]], nrows)
         outs[name] = col
         out_ptrs[c] = col.ptr.value
+
+    # candidate bytes back to back; slot s is [coffs[s], coffs[s + 1])
+    lens = np.zeros(ncols * MAX_DICT, dtype=np.uint32)
+    for slot, bs in cbytes:
+        lens[slot] = len(bs)
+    coffs[1:] = np.cumsum(lens)
+    blob = np.frombuffer(b"".join(bs for _, bs in cbytes) or b"\0",
+                         dtype=np.uint8)
 
     def up(a):
         b = DevBuffer(a.nbytes)
         shim.call("qk_h2d", b.ptr, a.ctypes.data_as(c_vp), c_u64(a.nbytes))
         return b
 
-    d_types, d_ptrs, d_cands, d_clens, d_nc = (
-        up(coltypes), up(out_ptrs), up(cands), up(clens), up(ncands))
+    d_types, d_ptrs, d_cands, d_clens, d_nc, d_blob, d_offs = (
+        up(coltypes), up(out_ptrs), up(cands), up(clens), up(ncands),
+        up(blob), up(coffs))
     err = DevBuffer(8)
     shim.call("qk_h2d", err.ptr,
               np.array([np.iinfo(np.uint64).max],
@@ -151,16 +179,18 @@ def read_csv(source, schema, sep="|", header=False, quote='"'):
               c_u64(data_start), pos.ptr, ctypes.c_uint8(ord(sep)),
               ctypes.c_uint8(qbyte if quoted else 0),
               ncols, d_types.ptr, d_ptrs.ptr, d_cands.ptr, d_clens.ptr,
-              d_nc.ptr, err.ptr)
+              d_nc.ptr, d_blob.ptr, d_offs.ptr, err.ptr)
     herr = np.zeros(1, dtype=np.uint64)
     shim.call("qk_d2h", herr.ctypes.data_as(c_vp), err.ptr, c_u64(8))
-    for b in (d_types, d_ptrs, d_cands, d_clens, d_nc, err, pos):
+    for b in (d_types, d_ptrs, d_cands, d_clens, d_nc, d_blob, d_offs, err,
+              pos):
         b.free()
     dev.free()
     if herr[0] != np.iinfo(np.uint64).max:
         for col in outs.values():
             col.free()
-        raise QkCsvError("row %d failed to parse (schema mismatch, "
-                         "unknown dict value, or >15-digit numeric)"
+        raise QkCsvError("row %d failed to parse (field count, bad "
+                         "quoting, unknown dict value, impossible date, "
+                         "or >15-digit numeric)"
                          % int(herr[0]))
     return outs

@@ -130,7 +130,8 @@ _SIGS = {
     "qk_csv_newlines": [c_vp, c_u64, c_u64, c_vp, c_vp, c_vp],
     "qk_csv_newlines_quoted": [c_vp, c_u64, c_u64, c_vp, c_u8, c_vp, c_vp],
     "qk_csv_parse": [c_vp, c_u64, c_vp, c_u64, c_vp, c_u8, c_u8,
-                     ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+                     ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                     c_vp],
     "qk_pq_plain_copy": [c_vp, c_u64, c_vp, c_vp, c_vp, c_u32],
     "qk_pq_rle_pages": [c_vp, c_u64, c_vp, c_vp, c_vp],
     "qk_pq_def_pages": [c_vp, c_u64, c_vp, c_vp, c_vp, c_vp],

@@ -111,13 +111,17 @@ def main():
         cands = np.zeros(4 * csv_gpu.MAX_DICT, dtype=np.uint64)
         clens = np.zeros(4 * csv_gpu.MAX_DICT, dtype=np.uint8)
         nc = np.array([0, 0, 0, 5], dtype=np.int32)
+        offs = np.zeros(4 * csv_gpu.MAX_DICT + 1, dtype=np.uint32)
         for j, v in enumerate(segs):
             w, ln = csv_gpu._dict_key(str(v))
             cands[3 * csv_gpu.MAX_DICT + j] = w
             clens[3 * csv_gpu.MAX_DICT + j] = ln
+            offs[3 * csv_gpu.MAX_DICT + j + 1] = len(str(v).encode())
+        offs[:] = np.cumsum(offs)
+        blob = np.frombuffer("".join(segs).encode(), dtype=np.uint8)
         ptrs = np.array([o.ptr.value for o in outs], dtype=np.uint64)
         ups = []
-        for a in (coltypes, ptrs, cands, clens, nc):
+        for a in (coltypes, ptrs, cands, clens, nc, blob, offs):
             b = DevBuffer(a.nbytes)
             shim.call("qk_h2d", b.ptr, a.ctypes.data_as(c_vp),
                       c_u64(a.nbytes))
@@ -129,7 +133,7 @@ def main():
         shim.call("qk_csv_parse", None, c_u64(n), dev.ptr, c_u64(0),
                   pos.ptr, ctypes.c_uint8(ord(",")), ctypes.c_uint8(0),
                   4, ups[0].ptr, ups[1].ptr, ups[2].ptr, ups[3].ptr,
-                  ups[4].ptr, err.ptr)
+                  ups[4].ptr, ups[5].ptr, ups[6].ptr, err.ptr)
         shim.call("qk_stream_sync", None)
         for b in ups + [err, cnt, pos] + outs:
             b.free()

@@ -46,6 +46,46 @@ def test_so_loads_and_exports_all_header_symbols():
     assert lib.qk_build_arch() == b"gfx950"
 
 
+def header_prototypes():
+    """name -> list of parameter texts, comments stripped"""
+    text = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
+    protos = {}
+    for m in re.finditer(r"^\s*(?:int|const char \*)\s*(qk_\w+)\s*"
+                         r"\(([^;]*)\)\s*;", text, re.M):
+        params = [p.strip() for p in m.group(2).split(",")]
+        protos[m.group(1)] = [] if params in ([""], ["void"]) else params
+    return protos
+
+
+def test_shim_signatures_match_header_prototypes():
+    """ctypes checks nothing: an argument missing from a shim signature
+    shifts every later one silently. Every signature the shim declares
+    must have the header's parameter count, and the CSV entry points the
+    header's exact parameter kinds."""
+    import ctypes as ct
+    from quokka_amd import shim
+    protos = header_prototypes()
+    both = set(shim._SIGS) & set(protos)    # int / const char * returns
+    assert len(both) >= 90, len(both)
+    for name in sorted(both):
+        assert len(shim._SIGS[name]) == len(protos[name]), name
+
+    def kind(param):
+        if "*" in param:
+            return ct.c_void_p
+        return {"uint64_t": ct.c_uint64, "uint8_t": ct.c_uint8,
+                "int": ct.c_int}[param.split()[0]]
+    for name in ("qk_csv_newlines", "qk_csv_newlines_quoted",
+                 "qk_csv_parse"):
+        assert [kind(p) for p in protos[name]] == shim._SIGS[name], name
+    # qk_csv_parse: (first 8 bytes, length) prefilter arrays, then the
+    # candidates' full bytes and offsets for the exact compare
+    names = [p.split()[-1].lstrip("*") for p in protos["qk_csv_parse"]]
+    assert names[-7:] == ["out_ptrs", "dict_cands", "dict_lens", "ncands",
+                          "dict_bytes", "dict_offs", "err_row"]
+    assert len(names) == 16
+
+
 def test_shim_imports_and_fails_loudly_without_gpu():
     from quokka_amd import shim
     assert shim.build_arch() == "gfx950"
