@@ -484,14 +484,29 @@ int qk_pq_plain_copy(void *stream, uint64_t ntiles, const uint64_t *tiles,
  * parsed AND expanded on-device, one wave per page (low-cardinality
  * columns emit millions of tiny runs — host-side run parsing cost
  * seconds, so the host ships one descriptor per page): ents = npages x
- * 6 u64 [src_byte_off (first run header, after the bit-width byte),
- * src_byte_end, dst_off, count, bit_width, idx_off]. Emits u32
+ * 8 u64 [src_off (first run header, after the bit-width byte), src_end,
+ * dst_off, count, bit_width, idx_off, dict_n, 0]. Emits u32
  * (index + idx_off) — idx_off rebases each chunk's dictionary into a
  * column-global concatenated dictionary so a whole multi-row-group
- * column expands in ONE launch. bw 0 => all idx_off. src_bytes needs
- * >= 8 bytes of slack after the end. */
+ * column expands in ONE launch. bit_width 0 => all idx_off, the stream
+ * is not read. src_bytes needs >= 8 bytes of slack after the end.
+ * err_dev = npages i64, written for every page: 0 ok; 1 stream truncated
+ * (a header varint that reaches src_end or is longer than 10 bytes, RLE
+ * value bytes or the used values of a bit-packed run past src_end, or
+ * the stream ends with values still owed); 2 an index >= dict_n among
+ * the `count` values used (padding bits of a clipped last group are not
+ * values); 3 bit_width > 32 or src_off > src_end, refused before any
+ * read. The first error in stream order ends the page. No byte at or
+ * past src_end influences out or err_dev; a bit-packed run is accepted
+ * when the bytes of the values used, ceil(n * bit_width / 8), lie before
+ * src_end even if the padding of its last group does not. A page writes
+ * only inside out[dst_off, dst_off + count), and every u32 it writes lies
+ * in [idx_off, idx_off + max(dict_n, 1)): an index >= dict_n is written
+ * as idx_off, so a gather stays in range before the host has seen
+ * err_dev. */
 int qk_pq_rle_pages(void *stream, uint64_t npages, const uint64_t *ents,
-                    const uint8_t *src_bytes, uint32_t *out);
+                    const uint8_t *src_bytes, uint32_t *out,
+                    int64_t *err_dev);
 
 /* ---- nullable columns: validity bitmaps ------------------------------ *
  * A nullable column is a dense value column of n rows (null slots hold 0)

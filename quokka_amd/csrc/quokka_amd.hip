@@ -2435,74 +2435,119 @@ extern "C" int qk_pq_plain_copy(void *stream, uint64_t ntiles,
   return 0;
 }
 // One WAVE per page: lane 0 parses the RLE/bit-packed run headers
-// (varints — inherently sequential within a page), broadcasts via
-// __shfl (wave-lockstep, no barriers), and all 64 lanes expand the run.
+// (varints — inherently sequential within a page), the wave reads lane
+// 0's header back as scalars (wave-lockstep, no barriers), and all 64
+// lanes expand the run.
 // Low-cardinality columns emit millions of tiny runs (measured 1.3M for
 // a 24M-row 2-value column) — parsing them in host Python cost seconds;
 // per-page parsing on-device leaves the host with ~1 descriptor per page.
+// Bounded like k_pq_def_pages: the run loop by pos < end and remaining,
+// the varint loop by npos < end and 10 bytes; every header advances pos
+// by >= 1 byte. No byte at or past `end` decides a value or the error
+// code (the 8-byte unaligned load may fetch such bytes, the mask drops
+// them). An index >= dict_n is written as 0, so the gather that follows
+// stays inside the chunk's dictionary whatever the host does with err.
+__device__ inline uint64_t qk_lane0_u64(uint64_t v) {
+  uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  uint32_t hi =
+      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
+#define QK_RLE_ERR_TRUNCATED 1
+#define QK_RLE_ERR_INDEX 2
+#define QK_RLE_ERR_DESC 3
 __global__ void __launch_bounds__(WAVE) k_pq_rle_pages(
     uint64_t npages, const uint64_t *__restrict__ ents,
-    const uint8_t *__restrict__ src, uint32_t *__restrict__ out) {
+    const uint8_t *__restrict__ src, uint32_t *__restrict__ out,
+    int64_t *__restrict__ err_out) {
+  const uint32_t lane = threadIdx.x;
   for (uint64_t pg = blockIdx.x; pg < npages; pg += gridDim.x) {
-    const uint64_t *E = ents + pg * 6;
-    uint64_t pos = E[0], end = E[1], dst = E[2], remaining = E[3];
-    uint32_t bw = (uint32_t)E[4];
-    uint32_t idx_off = (uint32_t)E[5];
-    if (bw == 0) {                       // all indices are 0, no stream
-      for (uint64_t i = threadIdx.x; i < remaining; i += WAVE)
+    const uint64_t *E = ents + pg * 8;
+    uint64_t pos = E[0], dst = E[2], remaining = E[3];
+    const uint64_t end = E[1], dict_n = E[6];
+    const uint32_t bw = (uint32_t)E[4];
+    const uint32_t idx_off = (uint32_t)E[5];
+    int err = 0;
+    if (E[4] > 32 || pos > end) {
+      err = QK_RLE_ERR_DESC;
+    } else if (bw == 0) {                // all indices are 0, no stream
+      for (uint64_t i = lane; i < remaining; i += WAVE)
         out[dst + i] = idx_off;
-      continue;
+      if (remaining && dict_n == 0) err = QK_RLE_ERR_INDEX;
+      remaining = 0;
     }
-    uint64_t mask = (1ull << bw) - 1;
-    while (remaining && pos < end) {
+    const uint64_t mask = (1ull << (bw & 63)) - 1;   // bw <= 32 past here
+    while (!err && remaining) {
+      if (pos >= end) { err = QK_RLE_ERR_TRUNCATED; break; }
       uint64_t h = 0, npos = pos, val = 0;
-      if (threadIdx.x == 0) {
+      uint32_t bad = 0;
+      if (lane == 0) {
         uint32_t shift = 0;
-        uint8_t b;
-        do {
-          b = src[npos++];
-          h |= (uint64_t)(b & 0x7F) << shift;
+        bad = QK_RLE_ERR_TRUNCATED;      // cleared by a terminating byte
+        while (npos < end && shift < 70) {
+          uint8_t b = src[npos++];
+          if (shift < 64) h |= (uint64_t)(b & 0x7F) << shift;
           shift += 7;
-        } while (b & 0x80);
-        if (!(h & 1)) {
+          if (!(b & 0x80)) { bad = 0; break; }
+        }
+        if (!bad && !(h & 1)) {
           uint32_t nb = (bw + 7) >> 3;
-          for (uint32_t i = 0; i < nb; i++)
-            val |= (uint64_t)src[npos++] << (8 * i);
+          if (end - npos < nb) bad = QK_RLE_ERR_TRUNCATED;
+          else
+            for (uint32_t i = 0; i < nb; i++)
+              val |= (uint64_t)src[npos++] << (8 * i);
         }
       }
-      h = (uint64_t)__shfl((long long)h, 0);
-      npos = (uint64_t)__shfl((long long)npos, 0);
+      // every lane is active here and lane 0 is the first: a scalar
+      // read of lane 0, no cross-lane permute
+      h = qk_lane0_u64(h);
+      npos = qk_lane0_u64(npos);
+      bad = (uint32_t)__builtin_amdgcn_readfirstlane((int)bad);
+      if (bad) { err = (int)bad; break; }
       uint64_t n;
       if (h & 1) {
         uint64_t ngroups = h >> 1;
-        n = qk_min_u64(ngroups * 8, remaining);
+        // ngroups * 8 may not fit in 64 bits; only min(., remaining) counts
+        n = ngroups >= remaining / 8 + ((remaining & 7) != 0)
+                ? remaining : ngroups * 8;
+        // the bytes of the n values used; the padding of a clipped last
+        // group may lie past `end` (older parquet-mr writers cut it off)
+        uint64_t need = (n * bw + 7) >> 3;
+        if (need > end - npos) { err = QK_RLE_ERR_TRUNCATED; break; }
         uint64_t bitbase = npos * 8;
-        for (uint64_t i = threadIdx.x; i < n; i += WAVE) {
+        bool oob = false;
+        for (uint64_t i = lane; i < n; i += WAVE) {
           uint64_t bit = bitbase + i * (uint64_t)bw;
           uint64_t w;
           __builtin_memcpy(&w, src + (bit >> 3), 8);  // unaligned, slack
-          out[dst + i] = (uint32_t)((w >> (bit & 7)) & mask) + idx_off;
+          uint32_t v = (uint32_t)((w >> (bit & 7)) & mask);
+          if (v >= dict_n) { oob = true; v = 0; }
+          out[dst + i] = v + idx_off;
         }
-        npos += ngroups * bw;
-      } else {
-        val = (uint64_t)__shfl((long long)val, 0);
+        if (__ballot(oob)) err = QK_RLE_ERR_INDEX;
+        npos += need;                    // == ngroups * bw unless clipped,
+      } else {                           // and a clipped run is the last
+        uint32_t v = (uint32_t)__builtin_amdgcn_readfirstlane((int)val);
         n = qk_min_u64(h >> 1, remaining);
-        for (uint64_t i = threadIdx.x; i < n; i += WAVE)
-          out[dst + i] = (uint32_t)val + idx_off;
+        if (n && v >= dict_n) { err = QK_RLE_ERR_INDEX; v = 0; }
+        for (uint64_t i = lane; i < n; i += WAVE)
+          out[dst + i] = v + idx_off;
       }
       dst += n;
       remaining -= n;
       pos = npos;
     }
+    if (lane == 0) err_out[pg] = err;
   }
 }
 extern "C" int qk_pq_rle_pages(void *stream, uint64_t npages,
                                const uint64_t *ents, const uint8_t *src_bytes,
-                               uint32_t *out) {
+                               uint32_t *out, int64_t *err_dev) {
   if (!npages) return 0;
   uint32_t blocks = (uint32_t)qk_min_u64(64 * 1024, npages);
   hipLaunchKernelGGL(k_pq_rle_pages, dim3(blocks), dim3(WAVE), 0,
-                     (hipStream_t)stream, npages, ents, src_bytes, out);
+                     (hipStream_t)stream, npages, ents, src_bytes, out,
+                     err_dev);
   QK_TRY("qk_pq_rle_pages", hipGetLastError());
   return 0;
 }

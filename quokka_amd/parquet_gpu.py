@@ -100,8 +100,11 @@ def _check_levels_v1(buf, pos, num_values, max_def, page_end=None):
 
 
 def _walk_rle(buf, pos, end, bitwidth, nvalues, dst0, ents):
-    """RLE/bit-packed hybrid (parquet encoding.md): append qk_pq_rle_expand
-    entries covering `nvalues` values starting at output row dst0."""
+    """RLE/bit-packed hybrid (parquet encoding.md), walked on the host:
+    append run entries (kind, dst, count, value | first bit, bit width)
+    covering `nvalues` values starting at output row dst0. The device
+    path (qk_pq_rle_pages) parses the runs itself; the CPU plan tests
+    keep this walker as their run-level model of a page."""
     seen = 0
     while seen < nvalues:
         if pos >= end:
@@ -129,6 +132,35 @@ def _walk_rle(buf, pos, end, bitwidth, nvalues, dst0, ents):
                 s += m
         seen += n
     return pos
+
+
+def _plain_page(data, pend, num_values, elem_size):
+    """Refuse a PLAIN page whose values run past the page."""
+    if data > pend or num_values * elem_size > pend - data:
+        raise QkParquetError("PLAIN values run past the page")
+
+
+def _dict_values(db, pos, end, num_values, dtype, is_ba):
+    """Dictionary page db[pos:end] -> np array (fixed width) or list of
+    str (BYTE_ARRAY); a page shorter than num_values entries is refused."""
+    short = QkParquetError("dictionary page shorter than its %d entries"
+                           % num_values)
+    if not is_ba:
+        if pos > end or num_values * dtype.itemsize > end - pos:
+            raise short
+        return np.frombuffer(db, dtype=dtype, count=num_values,
+                             offset=pos).copy()
+    vals = []
+    for _ in range(num_values):
+        if end - pos < 4:
+            raise short
+        ln = int.from_bytes(db[pos:pos + 4], "little")
+        pos += 4
+        if ln > end - pos:
+            raise short
+        vals.append(bytes(db[pos:pos + ln]).decode())
+        pos += ln
+    return vals
 
 
 class _Chunk:
@@ -190,9 +222,13 @@ class _Chunk:
                     raise QkParquetError("PLAIN BYTE_ARRAY unsupported; "
                                          "write with use_dictionary=True")
                 es = self.dtype.itemsize
+                _plain_page(data, pend, p.num_values, es)
                 self.plain_tiles.append(
                     _tile_block(data, row, p.num_values, es))
             elif p.encoding == ENC_RLE_DICT:
+                if data >= pend:
+                    raise QkParquetError("RLE_DICTIONARY page without a "
+                                         "bit-width byte")
                 bw = buf[data]
                 if bw > 32:
                     raise QkParquetError("index bit width %d" % bw)
@@ -207,19 +243,9 @@ class _Chunk:
             row += p.num_values
 
     def _load_dict(self, buf, p):
-        if self.is_ba:
-            vals = []
-            pos = p.data_off
-            for _ in range(p.num_values):
-                ln = int.from_bytes(buf[pos:pos + 4], "little")
-                pos += 4
-                vals.append(bytes(buf[pos:pos + ln]).decode())
-                pos += ln
-            self.dict_vals = vals
-        else:
-            self.dict_vals = np.frombuffer(
-                buf, dtype=self.dtype, count=p.num_values,
-                offset=p.data_off).copy()
+        self.dict_vals = _dict_values(buf, p.data_off,
+                                      p.data_off + p.data_len, p.num_values,
+                                      self.dtype, self.is_ba)
 
 
 def _def_page(p, off, size, row):
@@ -364,160 +390,159 @@ def _snappy_column(shim, raw, dev_file, cols_meta, max_def, dst0,
             off += ent["size"]
 
     scratch = DevBuffer(off + 8)
-    if copies:
-        tiles = np.asarray(copies, dtype=np.uint64)
-        dt = DevBuffer(tiles.nbytes)
-        shim.call("qk_h2d", dt.ptr, tiles.ctypes.data_as(c_vp),
-                  c_u64(tiles.nbytes))
-        shim.call("qk_pq_plain_copy", None, c_u64(len(tiles)), dt.ptr,
-                  dev_file.ptr, scratch.ptr, ctypes.c_uint32(1))
-        dt.free()
-    gresults = None
-    if gdescs:
-        ga = np.asarray(gdescs, dtype=np.uint64)
-        gd = DevBuffer(ga.nbytes)
-        shim.call("qk_h2d", gd.ptr, ga.ctypes.data_as(c_vp),
-                  c_u64(ga.nbytes))
-        gout = DevBuffer(len(gdescs) * 4 * 8)
-        shim.call("qk_gzip_pages", None, c_u64(len(gdescs)), gd.ptr,
-                  dev_file.ptr, scratch.ptr, gout.ptr)
-        shim.call("qk_stream_sync", None)
-        gresults = np.zeros(len(gdescs) * 4, dtype=np.int64)
-        shim.call("qk_d2h", gresults.ctypes.data_as(c_vp), gout.ptr,
-                  c_u64(gresults.nbytes))
-        gresults = gresults.reshape(-1, 4)
-        gd.free()
-        gout.free()
-        bad = np.nonzero(gresults[:, 1])[0]
-        if bad.size:
-            code = int(gresults[bad[0], 1])
-            raise QkParquetError(
-                "gzip page %d failed: %s" % (
-                    bad[0], {1: "corrupt stream",
-                             2: "uncompressed-length mismatch",
-                             3: "unsupported feature"}.get(code, code)))
-    results = None
-    if descs:
-        da = np.asarray(descs, dtype=np.uint64)
-        dd = DevBuffer(da.nbytes)
-        shim.call("qk_h2d", dd.ptr, da.ctypes.data_as(c_vp),
-                  c_u64(da.nbytes))
-        dout = DevBuffer(len(descs) * 4 * 8)
-        shim.call("qk_snappy_pages", None, c_u64(len(descs)), dd.ptr,
-                  dev_file.ptr, scratch.ptr, dout.ptr)
-        shim.call("qk_stream_sync", None)
-        results = np.zeros(len(descs) * 4, dtype=np.int64)
-        shim.call("qk_d2h", results.ctypes.data_as(c_vp), dout.ptr,
-                  c_u64(results.nbytes))
-        results = results.reshape(-1, 4)
-        dd.free()
-        dout.free()
-        bad = np.nonzero(results[:, 1])[0]
-        if bad.size:
-            code = int(results[bad[0], 1])
-            raise QkParquetError(
-                "snappy page %d failed: %s" % (
-                    bad[0], {1: "corrupt stream",
-                             2: "uncompressed-length mismatch",
-                             3: "page contains nulls"}.get(code, code)))
+    try:                    # a refusal below gives the scratch back
+        if copies:
+            tiles = np.asarray(copies, dtype=np.uint64)
+            dt = DevBuffer(tiles.nbytes)
+            shim.call("qk_h2d", dt.ptr, tiles.ctypes.data_as(c_vp),
+                      c_u64(tiles.nbytes))
+            shim.call("qk_pq_plain_copy", None, c_u64(len(tiles)), dt.ptr,
+                      dev_file.ptr, scratch.ptr, ctypes.c_uint32(1))
+            dt.free()
+        gresults = None
+        if gdescs:
+            ga = np.asarray(gdescs, dtype=np.uint64)
+            gd = DevBuffer(ga.nbytes)
+            shim.call("qk_h2d", gd.ptr, ga.ctypes.data_as(c_vp),
+                      c_u64(ga.nbytes))
+            gout = DevBuffer(len(gdescs) * 4 * 8)
+            shim.call("qk_gzip_pages", None, c_u64(len(gdescs)), gd.ptr,
+                      dev_file.ptr, scratch.ptr, gout.ptr)
+            shim.call("qk_stream_sync", None)
+            gresults = np.zeros(len(gdescs) * 4, dtype=np.int64)
+            shim.call("qk_d2h", gresults.ctypes.data_as(c_vp), gout.ptr,
+                      c_u64(gresults.nbytes))
+            gresults = gresults.reshape(-1, 4)
+            gd.free()
+            gout.free()
+            bad = np.nonzero(gresults[:, 1])[0]
+            if bad.size:
+                code = int(gresults[bad[0], 1])
+                raise QkParquetError(
+                    "gzip page %d failed: %s" % (
+                        bad[0], {1: "corrupt stream",
+                                 2: "uncompressed-length mismatch",
+                                 3: "unsupported feature"}.get(code, code)))
+        results = None
+        if descs:
+            da = np.asarray(descs, dtype=np.uint64)
+            dd = DevBuffer(da.nbytes)
+            shim.call("qk_h2d", dd.ptr, da.ctypes.data_as(c_vp),
+                      c_u64(da.nbytes))
+            dout = DevBuffer(len(descs) * 4 * 8)
+            shim.call("qk_snappy_pages", None, c_u64(len(descs)), dd.ptr,
+                      dev_file.ptr, scratch.ptr, dout.ptr)
+            shim.call("qk_stream_sync", None)
+            results = np.zeros(len(descs) * 4, dtype=np.int64)
+            shim.call("qk_d2h", results.ctypes.data_as(c_vp), dout.ptr,
+                      c_u64(results.nbytes))
+            results = results.reshape(-1, 4)
+            dd.free()
+            dout.free()
+            bad = np.nonzero(results[:, 1])[0]
+            if bad.size:
+                code = int(results[bad[0], 1])
+                raise QkParquetError(
+                    "snappy page %d failed: %s" % (
+                        bad[0], {1: "corrupt stream",
+                                 2: "uncompressed-length mismatch",
+                                 3: "page contains nulls"}.get(code, code)))
 
-    out_chunks = []
-    cur = None
-    scratch_host = {}       # chunk dict pages d2h'd lazily
+        out_chunks = []
+        cur = None
+        scratch_host = {}       # chunk dict pages d2h'd lazily
 
-    def _scratch_bytes(o, ln):
-        arr = np.empty(ln, dtype=np.uint8)
-        shim.call("qk_d2h", arr.ctypes.data_as(c_vp),
-                  ctypes.c_void_p(scratch.ptr.value + o), c_u64(ln))
-        return arr.tobytes()
+        def _scratch_bytes(o, ln):
+            arr = np.empty(ln, dtype=np.uint8)
+            shim.call("qk_d2h", arr.ctypes.data_as(c_vp),
+                      ctypes.c_void_p(scratch.ptr.value + o), c_u64(ln))
+            return arr.tobytes()
 
-    for ci, (col, pl, row0) in enumerate(chunk_pages):
-        cur = _PlanChunk(col, dtype, is_ba, col.num_values)
-        out_chunks.append(cur)
-    for ent in plans:
-        p = ent["page"]
-        cur = out_chunks[ent["chunk"]]
-        o = ent["off"]
-        if ent["kind"] == "dict" or (ent["kind"] == "raw"
-                                     and p.kind == T.PAGE_DICT):
-            if p.encoding not in (ENC_PLAIN, ENC_PLAIN_DICT):
-                raise QkParquetError("dict page encoding %d" % p.encoding)
-            if ent["kind"] == "dict":
-                db = _scratch_bytes(o, ent["size"])
+        for ci, (col, pl, row0) in enumerate(chunk_pages):
+            cur = _PlanChunk(col, dtype, is_ba, col.num_values)
+            out_chunks.append(cur)
+        for ent in plans:
+            p = ent["page"]
+            cur = out_chunks[ent["chunk"]]
+            o = ent["off"]
+            if ent["kind"] == "dict" or (ent["kind"] == "raw"
+                                         and p.kind == T.PAGE_DICT):
+                if p.encoding not in (ENC_PLAIN, ENC_PLAIN_DICT):
+                    raise QkParquetError("dict page encoding %d" % p.encoding)
+                if ent["kind"] == "dict":
+                    db = _scratch_bytes(o, ent["size"])
+                else:
+                    db = bytes(raw[p.data_off:p.data_off + p.data_len])
+                cur.dict_vals = _dict_values(db, 0, len(db), p.num_values,
+                                             dtype, is_ba)
+                continue
+            if mask:
+                # every kind of data page lies in the scratch at `o`, levels
+                # first: raw pages with their file length, the others with
+                # their uncompressed length
+                cur.def_pages.append(_def_page(p, o, ent["size"], ent["row"]))
+                continue
+            # data pages: find where values start + the RLE bit-width byte
+            if ent["kind"] == "v1":
+                if ent.get("gdesc") is not None:
+                    # GZIP v1 reaches here only with max_def == 0 (no
+                    # levels inside): values start at the page start
+                    data = o
+                    first = int(gresults[ent["gdesc"]][2])
+                else:
+                    r = results[ent["desc"]]
+                    data = o + int(r[0])
+                    first = int(r[2])
+                end = o + ent["size"]
+            elif ent["kind"] == "v2":
+                data = o + p.v2_levels_len
+                if ent.get("gdesc") is not None:
+                    first = int(gresults[ent["gdesc"]][2])
+                else:
+                    first = int(results[ent["desc"]][2])
+                end = o + ent["size"]
+            else:                                       # raw page in scratch
+                data_abs = p.data_off
+                if p.kind == T.PAGE_DATA:
+                    if max_def > 0:
+                        data_abs = _check_levels_v1(raw, data_abs,
+                                                    p.num_values, max_def,
+                                                    p.data_off + p.data_len)
+                else:
+                    if p.num_nulls:
+                        raise QkParquetError("page contains nulls")
+                    data_abs = p.data_off + p.v2_levels_len
+                data = o + (data_abs - p.data_off)
+                first = raw[data_abs] if data_abs < p.data_off + p.data_len \
+                    else -1
+                end = o + ent["size"]
+            if p.encoding == ENC_PLAIN:
+                if is_ba:
+                    raise QkParquetError("PLAIN BYTE_ARRAY unsupported; "
+                                         "write with use_dictionary=True")
+                _plain_page(data, end, p.num_values, dtype.itemsize)
+                cur.plain_tiles.append(
+                    _tile_block(data, ent["row"], p.num_values,
+                                dtype.itemsize))
+            elif p.encoding == ENC_RLE_DICT:
+                bw = first
+                if bw < 0 or data >= end:
+                    raise QkParquetError("RLE_DICTIONARY page without a "
+                                         "bit-width byte")
+                if bw > 32:
+                    raise QkParquetError("index bit width %d" % bw)
+                cur.rle_pages.append((data + 1, end, ent["row"],
+                                      p.num_values, bw))
             else:
-                db = bytes(raw[p.data_off:p.data_off + p.data_len])
-            if is_ba:
-                vals, pos = [], 0
-                for _ in range(p.num_values):
-                    ln = int.from_bytes(db[pos:pos + 4], "little")
-                    pos += 4
-                    vals.append(db[pos:pos + ln].decode())
-                    pos += ln
-                cur.dict_vals = vals
-            else:
-                cur.dict_vals = np.frombuffer(
-                    db, dtype=dtype, count=p.num_values).copy()
-            continue
-        if mask:
-            # every kind of data page lies in the scratch at `o`, levels
-            # first: raw pages with their file length, the others with
-            # their uncompressed length
-            cur.def_pages.append(_def_page(p, o, ent["size"], ent["row"]))
-            continue
-        # data pages: find where values start + the RLE bit-width byte
-        if ent["kind"] == "v1":
-            if ent.get("gdesc") is not None:
-                # GZIP v1 reaches here only with max_def == 0 (no
-                # levels inside): values start at the page start
-                data = o
-                first = int(gresults[ent["gdesc"]][2])
-            else:
-                r = results[ent["desc"]]
-                data = o + int(r[0])
-                first = int(r[2])
-            end = o + ent["size"]
-        elif ent["kind"] == "v2":
-            data = o + p.v2_levels_len
-            if ent.get("gdesc") is not None:
-                first = int(gresults[ent["gdesc"]][2])
-            else:
-                first = int(results[ent["desc"]][2])
-            end = o + ent["size"]
-        else:                                       # raw page in scratch
-            data_abs = p.data_off
-            if p.kind == T.PAGE_DATA:
-                if max_def > 0:
-                    data_abs = _check_levels_v1(raw, data_abs,
-                                                p.num_values, max_def,
-                                                p.data_off + p.data_len)
-            else:
-                if p.num_nulls:
-                    raise QkParquetError("page contains nulls")
-                data_abs = p.data_off + p.v2_levels_len
-            data = o + (data_abs - p.data_off)
-            first = raw[data_abs] if data_abs < p.data_off + p.data_len \
-                else -1
-            end = o + ent["size"]
-        if p.encoding == ENC_PLAIN:
-            if is_ba:
-                raise QkParquetError("PLAIN BYTE_ARRAY unsupported; "
-                                     "write with use_dictionary=True")
-            cur.plain_tiles.append(
-                _tile_block(data, ent["row"], p.num_values,
-                            dtype.itemsize))
-        elif p.encoding == ENC_RLE_DICT:
-            bw = first
-            if bw < 0 or bw > 32:
-                raise QkParquetError("index bit width %d" % bw)
-            cur.rle_pages.append((data + 1, end, ent["row"],
-                                  p.num_values, bw))
-        else:
-            raise QkParquetError("data page encoding %d" % p.encoding)
+                raise QkParquetError("data page encoding %d" % p.encoding)
+    except BaseException:
+        scratch.free()
+        raise
     return out_chunks, scratch
 
 
 def _upload(shim, host_bytes):
-    """File bytes -> device, with the 8-byte slack qk_pq_rle_expand needs."""
+    """File bytes -> device, with the 8-byte slack qk_pq_rle_pages needs."""
     from .shim import DevBuffer, c_u64, c_vp
     arr = np.frombuffer(host_bytes, dtype=np.uint8)
     buf = DevBuffer(len(arr) + 8)
@@ -528,7 +553,10 @@ def _upload(shim, host_bytes):
 _DEF_ERR = {1: "definition levels run past the page",
             2: "definition levels truncated",
             3: "definition level above 1 (nested schemas unsupported)"}
-_V1 = (1 << 64) - 1      # qk_pq_def_pages: v2_levels_len marker of a v1 page
+_RLE_ERR = {1: "index stream truncated",
+            2: "index at or above the dictionary length",
+            3: "bit width above 32 or stream offsets reversed"}
+_V1 = (1 << 64) - 1     # qk_pq_def_pages: v2_levels_len marker of a v1 page
 
 
 def _def_descs(chunks):
@@ -617,10 +645,10 @@ def _decode_masked(shim, src, chunks, total):
         dout.free()
     try:
         nonnull = _dense_plan(chunks, results)
+        dense = _decode_column(shim, src, chunks, nonnull)
     except QkParquetError:
         valid.free()
         raise
-    dense = _decode_column(shim, src, chunks, nonnull)
     vals = None
     if chunks[0].is_ba:
         dense, vals = dense
@@ -731,9 +759,11 @@ def read_table(source, columns=None, nulls="raise"):
                                                  payload, max_def, 0, mask)
                 assert sum(ch.n for ch in chunks) == total
                 decode = _decode_masked if masked else _decode_column
-                out[names[ci]] = decode(shim, scratch, chunks, total)
-                shim.call("qk_stream_sync", None)
-                scratch.free()
+                try:
+                    out[names[ci]] = decode(shim, scratch, chunks, total)
+                    shim.call("qk_stream_sync", None)
+                finally:
+                    scratch.free()
             elif masked:
                 out[names[ci]] = _decode_masked(shim, dev_file, payload,
                                                 total)
@@ -742,11 +772,56 @@ def read_table(source, columns=None, nulls="raise"):
                                                 total)
         shim.call("qk_stream_sync", None)
         return out
+    except QkParquetError:
+        # columns decoded before the one that was refused
+        for c in out.values():
+            (c[0] if isinstance(c, tuple) else c).free()
+        raise
     finally:
         dev_file.free()
         if isinstance(source, str):
             raw.close()
             fh.close()
+
+
+def _rle_ents(chunks):
+    """qk_pq_rle_pages descriptors of one column (npages x 8 u64
+    [src_off, src_end, dst_off, count, bit_width, idx_off, dict_n, 0]):
+    idx_off rebases each chunk's dictionary into the column-global
+    concatenation, dict_n is that chunk's own dictionary length. Returns
+    (ents, per-chunk dictionary parts, BYTE_ARRAY value -> global code).
+    Pages that hold no value are dropped; a chunk whose pages hold values
+    but whose dictionary is empty is refused, so the gather never meets
+    an empty dictionary."""
+    is_ba = chunks[0].is_ba
+    pages = []
+    dict_parts = []
+    glob = {}
+    if is_ba:
+        for ch in chunks:
+            for v in ch.dict_vals or []:
+                glob.setdefault(v, len(glob))
+    dict_off = 0
+    for ch in chunks:
+        rle = [pg for pg in ch.rle_pages if pg[3]]
+        if not rle:
+            continue
+        if ch.dict_vals is None:
+            raise QkParquetError("RLE_DICTIONARY page without dictionary "
+                                 "page")
+        if not len(ch.dict_vals):
+            raise QkParquetError("RLE_DICTIONARY page with values but an "
+                                 "empty dictionary")
+        for (s, e, d, c, bw) in rle:
+            pages.append((s, e, d, c, bw, dict_off, len(ch.dict_vals), 0))
+        if is_ba:
+            dict_parts.append(np.asarray([glob[v] for v in ch.dict_vals],
+                                         dtype=np.int32))
+        else:
+            dict_parts.append(np.ascontiguousarray(ch.dict_vals))
+        dict_off += len(ch.dict_vals)
+    return (np.asarray(pages, dtype=np.uint64).reshape(-1, 8), dict_parts,
+            glob)
 
 
 def _decode_column(shim, dev_file, chunks, total):
@@ -764,43 +839,26 @@ def _decode_column(shim, dev_file, chunks, total):
     import ctypes
     from .shim import DevBuffer, DevColumn, c_u64, c_vp
     is_ba = chunks[0].is_ba
-    pages = []
-    dict_parts = []
-    if is_ba:
-        glob = {}
-        for ch in chunks:
-            for v in ch.dict_vals or []:
-                glob.setdefault(v, len(glob))
-    dict_off = 0
-    for ch in chunks:
-        if not ch.rle_pages:
-            continue
-        if ch.dict_vals is None:
-            raise QkParquetError("RLE_DICTIONARY page without dictionary "
-                                 "page")
-        for (s, e, d, c, bw) in ch.rle_pages:
-            pages.append((s, e, d, c, bw, dict_off))
-        if is_ba:
-            dict_parts.append(np.asarray([glob[v] for v in ch.dict_vals],
-                                         dtype=np.int32))
-        else:
-            dict_parts.append(np.ascontiguousarray(ch.dict_vals))
-        dict_off += len(ch.dict_vals)
+    ents, dict_parts, glob = _rle_ents(chunks)
 
     dt = np.dtype(np.uint32) if is_ba else chunks[0].dtype
     col_out = DevColumn(dt, max(1, total))
     col_out.n = total
-    if pages:
-        ents = np.asarray(pages, dtype=np.uint64)
+    errs = derr = None
+    if len(ents):
         dents = DevBuffer(ents.nbytes)
         shim.call("qk_h2d", dents.ptr, ents.ctypes.data_as(c_vp),
                   c_u64(ents.nbytes))
         idx = DevColumn(np.uint32, max(1, total))
+        errs = np.zeros(len(ents), dtype=np.int64)
+        derr = DevBuffer(errs.nbytes)
         # rows covered only by PLAIN pages keep index 0 here; the final
         # plain-copy launch overwrites them with decoded values
         shim.call("qk_dmemset", idx.ptr, 0, c_u64(4 * max(1, total)))
         shim.call("qk_pq_rle_pages", None, c_u64(len(ents)), dents.ptr,
-                  dev_file.ptr, idx.ptr)
+                  dev_file.ptr, idx.ptr, derr.ptr)
+        # the kernel keeps every index inside its chunk's dictionary, so
+        # the gather is safe before the error table has been looked at
         dcat = DevColumn.from_numpy(np.concatenate(dict_parts))
         gather = {8: "qk_gather_i64", 4: "qk_gather_i32"}[dt.itemsize]
         shim.call(gather, None, c_u64(total), idx.ptr, dcat.ptr,
@@ -819,6 +877,18 @@ def _decode_column(shim, dev_file, chunks, total):
                   dev_file.ptr, col_out.ptr,
                   ctypes.c_uint32(dt.itemsize))
         dtile.free()
+    if derr is not None:
+        # one read-back per dictionary column, after all its launches
+        shim.call("qk_stream_sync", None)
+        shim.call("qk_d2h", errs.ctypes.data_as(c_vp), derr.ptr,
+                  c_u64(errs.nbytes))
+        derr.free()
+        bad = np.nonzero(errs)[0]
+        if bad.size:
+            col_out.free()
+            code = int(errs[bad[0]])
+            raise QkParquetError("dictionary index page %d: %s"
+                                 % (bad[0], _RLE_ERR.get(code, code)))
     if is_ba:
         return col_out, sorted(glob, key=glob.get)
     return col_out

@@ -133,7 +133,7 @@ _SIGS = {
                      ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                      c_vp],
     "qk_pq_plain_copy": [c_vp, c_u64, c_vp, c_vp, c_vp, c_u32],
-    "qk_pq_rle_pages": [c_vp, c_u64, c_vp, c_vp, c_vp],
+    "qk_pq_rle_pages": [c_vp, c_u64, c_vp, c_vp, c_vp, c_vp],
     "qk_pq_def_pages": [c_vp, c_u64, c_vp, c_vp, c_vp, c_vp],
     "qk_valid_expand": [c_vp, c_u64, c_vp, c_vp, c_vp, c_u32],
     "qk_valid_to_u8": [c_vp, c_u64, c_vp, c_vp],

@@ -60,8 +60,8 @@ def header_prototypes():
 def test_shim_signatures_match_header_prototypes():
     """ctypes checks nothing: an argument missing from a shim signature
     shifts every later one silently. Every signature the shim declares
-    must have the header's parameter count, and the CSV entry points the
-    header's exact parameter kinds."""
+    must have the header's parameter count, and the CSV and Parquet page
+    entry points the header's exact parameter kinds."""
     import ctypes as ct
     from quokka_amd import shim
     protos = header_prototypes()
@@ -76,8 +76,11 @@ def test_shim_signatures_match_header_prototypes():
         return {"uint64_t": ct.c_uint64, "uint8_t": ct.c_uint8,
                 "int": ct.c_int}[param.split()[0]]
     for name in ("qk_csv_newlines", "qk_csv_newlines_quoted",
-                 "qk_csv_parse"):
+                 "qk_csv_parse", "qk_pq_rle_pages", "qk_pq_def_pages"):
         assert [kind(p) for p in protos[name]] == shim._SIGS[name], name
+    # qk_pq_rle_pages ends with the per-page error table
+    assert [p.split()[-1].lstrip("*") for p in protos["qk_pq_rle_pages"]] \
+        == ["stream", "npages", "ents", "src_bytes", "out", "err_dev"]
     # qk_csv_parse: (first 8 bytes, length) prefilter arrays, then the
     # candidates' full bytes and offsets for the exact compare
     names = [p.split()[-1].lstrip("*") for p in protos["qk_csv_parse"]]

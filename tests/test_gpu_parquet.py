@@ -1,6 +1,6 @@
 """GPU parity for the Parquet decode kernels: the same file shapes the
 CPU plan tests pin (tests/test_parquet_cpu.py) decoded by the real
-qk_pq_plain_copy / qk_pq_rle_expand kernels via parquet_gpu.read_table,
+qk_pq_plain_copy / qk_pq_rle_pages kernels via parquet_gpu.read_table,
 compared against pyarrow's decode (the reference's reader,
 pyquokka/dataset.py). Ends with Parquet -> HBM -> Q1 vs the oracle."""
 import io

@@ -81,7 +81,8 @@ def sim_rle_pages(raw, pages):
 
 
 def sim_rle(raw, ents):
-    """Simulate qk_pq_rle_expand (including the 8-byte unaligned load)."""
+    """Simulate the expansion qk_pq_rle_pages does per run (including the
+    8-byte unaligned load)."""
     e = np.asarray(ents, dtype=np.uint64)
     base = int(e[:, 1].min())
     nv = int(e[:, 2].sum())

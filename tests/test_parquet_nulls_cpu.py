@@ -3,9 +3,12 @@ simulators of qk_pq_def_pages and qk_valid_expand run over the real plan
 (_Chunk(mask=True) -> _def_descs -> _dense_plan) and the result is
 compared with pyarrow's decode of the same file: values where valid, and
 the is_valid() mask. Hand-built level blocks check that a corrupt stream
-ends in an error code and never reads past its page. The GPU suite runs
-the same shapes through the kernels."""
+ends in an error code and never reads past its page; the blocks live in
+tests/_pq_hybrid_cases.py and tests/test_gpu_pq_hybrid.py runs the same
+bytes through the kernel."""
 import io
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -15,92 +18,12 @@ import pyarrow.parquet as pq  # noqa: E402
 
 from quokka_amd import parquet_gpu as P  # noqa: E402
 
-ERR_PAST, ERR_TRUNC, ERR_LEVEL = 1, 2, 3
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _pq_hybrid_cases as C  # noqa: E402
+from _pq_hybrid_cases import sim_def_pages  # noqa: E402
 
-
-class Guard(bytes):
-    """bytes that refuse an index at or past `limit` — the page end."""
-    limit = None
-
-    def __getitem__(self, i):
-        assert isinstance(i, int) and 0 <= i < self.limit, \
-            "read at %r, page ends at %d" % (i, self.limit)
-        return bytes.__getitem__(self, i)
-
-
-def sim_def_pages(src, descs, valid_words):
-    """qk_pq_def_pages, lane by lane semantics folded into row loops.
-    valid_words: np.uint64 bitmap, pre-zeroed, OR-ed into. Returns the
-    npages x 4 result table."""
-    out = np.zeros((len(descs), 4), dtype=np.int64)
-    for pg, (pos, page_end, v2len, row0, nrows, _) in enumerate(
-            np.asarray(descs, dtype=np.uint64).tolist()):
-        err = 0
-        if v2len == P._V1:
-            if pos > page_end or page_end - pos < 4:
-                err, end = ERR_PAST, pos
-            else:
-                ln = int.from_bytes(bytes(src[pos + i] for i in range(4)),
-                                    "little")
-                pos += 4
-                end = pos + ln
-                if end > page_end:
-                    err = ERR_PAST
-        else:
-            end = pos + v2len
-            if pos > page_end or v2len > page_end - pos:
-                err = ERR_PAST
-        row, remaining, nonnull = row0, nrows, 0
-        steps = 0
-        while not err and remaining and pos < end:
-            steps += 1
-            assert steps <= end, "run loop does not advance"
-            h, shift, npos, bad = 0, 0, pos, ERR_TRUNC
-            while npos < end and shift < 64:
-                b = src[npos]
-                npos += 1
-                h |= (b & 0x7F) << shift
-                shift += 7
-                if not b & 0x80:
-                    bad = 0
-                    break
-            val = 0
-            if not bad and not h & 1:
-                if npos >= end:
-                    bad = ERR_TRUNC
-                else:
-                    val = src[npos]
-                    npos += 1
-                    if val > 1:
-                        bad = ERR_LEVEL
-            if bad:
-                err = bad
-                break
-            if h & 1:
-                ngroups = h >> 1
-                if ngroups > end - npos:
-                    err = ERR_TRUNC
-                    break
-                n = min(ngroups * 8, remaining)
-                bits = [(src[npos + (i >> 3)] >> (i & 7)) & 1
-                        for i in range(n)]
-                npos += ngroups
-            else:
-                n = min(h >> 1, remaining)
-                bits = [val] * n
-            for i, b in enumerate(bits):
-                if b:
-                    r = row + i
-                    valid_words[r >> 6] |= np.uint64(1 << (r & 63))
-                    nonnull += 1
-            row += n
-            remaining -= n
-            pos = npos
-        if not err and remaining:
-            err = ERR_TRUNC
-        first = src[end] if not err and end < page_end else -1
-        out[pg] = (nonnull, end, err, first)
-    return out
+ERR_PAST, ERR_TRUNC, ERR_LEVEL = C.DEF_PAST, C.DEF_TRUNC, C.DEF_LEVEL
+assert C.V1 == P._V1
 
 
 def sim_valid_expand(valid_words, dense, n):
@@ -290,7 +213,7 @@ def run_block(block, nrows, v2len=None, page_len=None):
     """One page made of `block` alone (page_len defaults to its length),
     followed by poison the simulator must not touch."""
     page_len = len(block) if page_len is None else page_len
-    src = Guard(block + b"\xAA" * 64)
+    src = C.Guard(block + b"\xAA" * 64)
     src.limit = page_len
     words = np.zeros(P_valid_words(nrows), dtype=np.uint64)
     desc = [(0, page_len, P._V1 if v2len is None else v2len, 0, nrows, 0)]
@@ -298,67 +221,45 @@ def run_block(block, nrows, v2len=None, page_len=None):
     return res, words
 
 
-def v1(levels):
-    return len(levels).to_bytes(4, "little") + levels
-
-
-def vi(x):
-    """ULEB128 varint, the run-header encoding."""
-    out = bytearray()
-    while True:
-        out.append((x & 0x7F) | (0x80 if x > 0x7F else 0))
-        x >>= 7
-        if not x:
-            return bytes(out)
+def run_cases(err):
+    """Every block of the shared def_pages list (tests/_pq_hybrid_cases.py;
+    tests/test_gpu_pq_hybrid.py runs the same bytes through the kernel)
+    that must end in `err`, with everything the case pins asserted."""
+    cases = [c for c in C.def_cases() if c.err == err]
+    for c in cases:
+        res, words = run_block(c.block, c.nrows, c.v2len, c.page_len)
+        assert res[2] == c.err, c
+        if c.res3 is not None:
+            assert res.tolist()[:3] == c.res3, c
+        if c.words is not None:
+            assert [int(w) for w in words[:len(c.words)]] == c.words, c
+            assert not words[len(c.words):].any(), c
+        if c.clean:
+            assert not words.any(), c
+    return [c.name for c in cases]
 
 
 def test_good_blocks():
-    # RLE run of 100 ones
-    res, words = run_block(v1(vi(100 << 1) + b"\x01"), 100)
-    assert res.tolist()[:3] == [100, 7, 0]
-    assert int(words[0]) == (1 << 64) - 1 and int(words[1]) == (1 << 36) - 1
-    # bit-packed: 2 groups, 13 rows used
-    res, words = run_block(v1(bytes([(2 << 1) | 1, 0b10110101, 0xFF])), 13)
-    assert res.tolist()[:3] == [10, 7, 0]
-    assert int(words[0]) == 0b1111110110101
-    # v2: no prefix
-    res, _ = run_block(bytes([7 << 1, 0]), 7, v2len=2)
-    assert res.tolist()[:3] == [0, 2, 0]
+    names = run_cases(0)
+    assert {"rle-100-ones", "packed-2-groups-13-rows",
+            "v2-no-prefix"} <= set(names)
 
 
 def test_truncated_run_header():
-    # varint continuation bit set on the block's last byte
-    res, _ = run_block(v1(bytes([0x80])), 50)
-    assert res[2] == ERR_TRUNC
-    # RLE header without its value byte
-    res, _ = run_block(v1(bytes([50 << 1])), 50)
-    assert res[2] == ERR_TRUNC
-    # bit-packed header that claims more groups than the block holds
-    res, _ = run_block(v1(bytes([(9 << 1) | 1, 0xFF, 0xFF])), 50)
-    assert res[2] == ERR_TRUNC
-    # the stream ends before the page's rows are covered
-    res, _ = run_block(v1(bytes([10 << 1, 1])), 50)
-    assert res[2] == ERR_TRUNC
-    # zero-length runs advance and end, they cannot spin
-    res, _ = run_block(v1(bytes([0, 1] * 20)), 50)
-    assert res[2] == ERR_TRUNC
+    assert run_cases(ERR_TRUNC) == [
+        "varint-continues-on-last-byte", "rle-without-value-byte",
+        "packed-groups-past-block", "covers-10-of-50",
+        "twenty-zero-length-runs", "covers-150-of-200"]
 
 
 def test_length_prefix_past_page_end():
-    block = (1000).to_bytes(4, "little") + vi(100 << 1) + b"\x01"
-    res, words = run_block(block, 100)
-    assert res[2] == ERR_PAST and not words.any()
-    # a page too short for the prefix itself
-    res, _ = run_block(b"\x02\x00", 10)
-    assert res[2] == ERR_PAST
-    # v2 length from the header past the page
-    res, _ = run_block(bytes([7 << 1, 1]), 7, v2len=40)
-    assert res[2] == ERR_PAST
+    assert run_cases(ERR_PAST) == [
+        "prefix-past-page", "page-shorter-than-prefix",
+        "v2-length-past-page"]
 
 
 def test_level_above_one():
-    res, _ = run_block(v1(vi(100 << 1) + b"\x02"), 100)
-    assert res[2] == ERR_LEVEL
+    assert run_cases(ERR_LEVEL) == ["level-2"]
 
 
 def test_dense_plan_refuses_errors_and_header_mismatch():
