@@ -164,8 +164,11 @@ extern "C" int qk_jit_filter_build(const char *expr, int ncols,
   if (hiprtcCreateProgram(&prog, src.c_str(), "qk_jit_filter.cu", 0,
                           nullptr, nullptr) != HIPRTC_SUCCESS)
     return j_fail("qk_jit_filter_build", "hiprtcCreateProgram failed");
-  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17"};
-  hiprtcResult rc = hiprtcCompileProgram(prog, 3, opts);
+  // -ffp-contract=off: a fused multiply-add is not bit-identical to the
+  // reference's multiply then add
+  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17",
+                        "-ffp-contract=off"};
+  hiprtcResult rc = hiprtcCompileProgram(prog, 4, opts);
   if (rc != HIPRTC_SUCCESS) {
     size_t lsz = 0;
     hiprtcGetProgramLogSize(prog, &lsz);
@@ -463,8 +466,8 @@ extern "C" int qk_jit_agg_build(const char *pred, const char *group_expr,
                           nullptr) != HIPRTC_SUCCESS)
     return j_fail("qk_jit_agg_build", "hiprtcCreateProgram failed");
   const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17",
-                        "-munsafe-fp-atomics"};
-  hiprtcResult rc = hiprtcCompileProgram(prog, 4, opts);
+                        "-munsafe-fp-atomics", "-ffp-contract=off"};
+  hiprtcResult rc = hiprtcCompileProgram(prog, 5, opts);
   if (rc != HIPRTC_SUCCESS) {
     size_t lsz = 0;
     hiprtcGetProgramLogSize(prog, &lsz);
@@ -558,8 +561,9 @@ extern "C" int qk_jit_map_build(const char *expr, int ncols,
   if (hiprtcCreateProgram(&prog, src.c_str(), "qk_jit_map.cu", 0, nullptr,
                           nullptr) != HIPRTC_SUCCESS)
     return j_fail("qk_jit_map_build", "hiprtcCreateProgram failed");
-  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17"};
-  if (hiprtcCompileProgram(prog, 3, opts) != HIPRTC_SUCCESS) {
+  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17",
+                        "-ffp-contract=off"};
+  if (hiprtcCompileProgram(prog, 4, opts) != HIPRTC_SUCCESS) {
     size_t lsz = 0;
     hiprtcGetProgramLogSize(prog, &lsz);
     std::string log(lsz, '\0');

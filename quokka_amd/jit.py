@@ -22,7 +22,10 @@ reference's TPC-H workload uses (apps/tpc-h/tpch.py filter_sql calls):
   it as one more input, `(vK) != 0` (or `== 0` for the negated forms), so
   AND/OR/NOT and numeric terms compose around it unchanged. IN lists on
   raw string columns are not supported.
-  arithmetic   + - * / on columns and literals
+  arithmetic   + - * / and unary minus on columns and literals: `/` is
+               always f64 division (7 / 2 is 3.5, as Polars and DuckDB
+               divide), integer + - * are carried in long long (exact
+               whenever the true result fits in int64)
   literals     ints, floats, date 'YYYY-MM-DD' (+/- interval 'N'
                day/month/year, evaluated host-side to date32 days),
                single-quoted strings (equality on dictionary-coded
@@ -123,6 +126,48 @@ def _date_add(days, n, unit):
         # SQL interval semantics: clamp the day to the target month's end
         d = datetime.date(y, m, min(d.day, _last_dom(y, m)))
     return (d - _EPOCH).days
+
+
+_I64_MIN, _I64_MAX = -(1 << 63), (1 << 63) - 1
+_PY_CMP = {"<": lambda x, y: x < y, "<=": lambda x, y: x <= y,
+           ">": lambda x, y: x > y, ">=": lambda x, y: x >= y,
+           "==": lambda x, y: x == y, "!=": lambda x, y: x != y}
+
+
+def _lit_val(text):
+    """Python value of a literal's text (a repr, maybe parenthesized)."""
+    return eval(text, {"__builtins__": {}})
+
+
+def _lit_text(v):
+    if isinstance(v, float):
+        if v != v or v in (float("inf"), float("-inf")):
+            raise ValueError("literal arithmetic leaves the f64 range")
+        return repr(v)
+    return repr(v)
+
+
+def _fits_i64(v):
+    return isinstance(v, float) or _I64_MIN <= v <= _I64_MAX
+
+
+def _c_lit(text, as_double=False):
+    """C text of a literal. Any int inside int64 but INT64_MIN is its own
+    text (C types it int, long or long long: signed). INT64_MIN is spelt
+    without the unsigned constant 9223372036854775808; an integer outside
+    int64 is only ever emitted as the double it converts to."""
+    v = _lit_val(text)
+    if isinstance(v, float) or _I64_MIN < v <= _I64_MAX:
+        return text
+    if v == _I64_MIN:
+        return "(-9223372036854775807LL - 1)"
+    if as_double:
+        try:
+            return _lit_text(float(v))
+        except OverflowError:
+            raise ValueError("integer literal leaves the f64 range")
+    raise ValueError("integer literal %d is outside int64 in integer "
+                     "arithmetic" % v)
 
 
 class Translator:
@@ -345,7 +390,7 @@ class Translator:
             except ValueError:
                 self.i = save
                 self._touched = []
-        left, _ = self.p_arith()
+        left, lt = self.p_arith()
         t = self.peek()
         if t and t.kind == "IS":
             return self._p_is_null()
@@ -357,22 +402,38 @@ class Translator:
             if neg:
                 self.take("IN")
             els = self._p_in_list(allow_str=False)
-            body = " || ".join("((%s) == (%s))" % (left, repr(e))
-                               for e in els)
+            # an element no value of `left` can equal (an integer outside
+            # int64 against an integer operand) folds to (0) and is dropped
+            terms = [self._cmp(left, lt, "==", _lit_text(e), "lit")
+                     for e in els]
+            body = " || ".join("(%s)" % c for c in terms if c != "(0)") \
+                or "(0)"
             return ("!(%s)" if neg else "(%s)") % body
         if t and t.kind == "BETWEEN":
             self.take()
-            lo, _ = self.p_arith()
+            n_left = len(self._touched)
+            lo, lot = self.p_arith()
+            n_lo = len(self._touched)
             self.take("AND")
-            hi, _ = self.p_arith()
-            return "(((%s) >= (%s)) && ((%s) <= (%s)))" % (left, lo,
-                                                            left, hi)
+            hi, hit = self.p_arith()
+            ge = self._cmp(left, lt, ">=", lo, lot)
+            le = self._cmp(left, lt, "<=", hi, hit)
+            if len(self._touched) > n_left:
+                # a nullable bound: BETWEEN is the Kleene AND of its two
+                # comparisons, each unknown only through its own operands
+                # (lo NULL and left > hi is FALSE, not unknown)
+                tl, fl = self._leaf3(ge, self._touched[:n_lo])
+                th, fh = self._leaf3(le, self._touched[:n_left]
+                                     + self._touched[n_lo:])
+                return ("((%s) && (%s))" % (tl, th),
+                        "((%s) || (%s))" % (fl, fh))
+            return "((%s) && (%s))" % (ge, le)
         op = self.take("op").val
         if op not in ("<", "<=", ">", ">=", "=", "==", "<>", "!="):
             raise ValueError("expected comparison operator, got %r" % op)
         cop = {"=": "==", "<>": "!="}.get(op, op)
-        right, _ = self.p_arith()
-        return "(%s) %s (%s)" % (left, cop, right)
+        right, rt = self.p_arith()
+        return self._cmp(left, lt, cop, right, rt)
 
     def _p_in_list(self, allow_str):
         """Parse IN's '(v1, v2, ...)' — literal numbers (and strings when
@@ -422,16 +483,65 @@ class Translator:
             left, lt = self._fold(left, lt, op, right, rt)
         return left, lt
 
+    # Arithmetic operands carry a type tag: "lit" (a folded literal, its
+    # text the Python repr), "n" (an i32/u8 column), "l" (long long) or
+    # "d" (double). Integer arithmetic is carried in long long, so it is
+    # exact whenever the true result fits in int64; `/` is always f64
+    # division, as the reference's SQL engines divide.
     @staticmethod
     def _fold(l, lt, op, r, rt):
         # host-fold literal arithmetic in f64, exactly as the reference
         # SQL engine evaluates constant expressions (bit-identical bounds)
         if lt == "lit" and rt == "lit":
-            v = eval("(%s) %s (%s)" % (l, "/" if op == "/" else op, r))
-            return repr(float(v)) if isinstance(v, float) else repr(v), "lit"
-        if lt == "date" and rt == "interval":
-            raise ValueError("interval arithmetic handled in p_atom")
-        return "(%s) %s (%s)" % (l, op, r), "mixed"
+            try:
+                v = eval("(%s) %s (%s)" % (l, op, r))
+            except (ZeroDivisionError, OverflowError) as e:
+                raise ValueError("cannot fold (%s) %s (%s): %s"
+                                 % (l, op, r, e))
+            return _lit_text(v), "lit"
+        lf = lt == "d" or (lt == "lit" and isinstance(_lit_val(l), float))
+        rf = rt == "d" or (rt == "lit" and isinstance(_lit_val(r), float))
+        if lt == "lit":
+            l = _c_lit(l, as_double=rf)
+        if rt == "lit":
+            r = _c_lit(r, as_double=lf)
+        if lf or rf:
+            return "(%s) %s (%s)" % (l, op, r), "d"
+        if op == "/":
+            return "(double)(%s) / (double)(%s)" % (l, r), "d"
+        if lt == "n" or rt == "n":
+            if lt == "n":
+                l = "(long long)(%s)" % l
+            if rt == "n":
+                r = "(long long)(%s)" % r
+        return "(%s) %s (%s)" % (l, op, r), "l"
+
+    @staticmethod
+    def _cmp(l, lt, cop, r, rt):
+        """Two-valued C text of `l cop r`. An integer literal outside
+        int64 never reaches the C text: against an integer operand the
+        comparison is decided here, as the mathematical integers decide
+        it; against a double it becomes the double it converts to."""
+        lv = _lit_val(l) if lt == "lit" else None
+        rv = _lit_val(r) if rt == "lit" else None
+        if lt == "lit" and rt == "lit":
+            if _fits_i64(lv) and _fits_i64(rv):
+                return "(%s) %s (%s)" % (_c_lit(l), cop, _c_lit(r))
+            return "(1)" if _PY_CMP[cop](lv, rv) else "(0)"
+        if lt == "lit" and not _fits_i64(lv):
+            if rt == "d":
+                return "(%s) %s (%s)" % (_c_lit(l, True), cop, r)
+            return "(1)" if _PY_CMP[cop](lv, 0) else "(0)"
+        if rt == "lit" and not _fits_i64(rv):
+            if lt == "d":
+                return "(%s) %s (%s)" % (l, cop, _c_lit(r, True))
+            # every int64 lies on the same side of rv as 0 does
+            return "(1)" if _PY_CMP[cop](0, rv) else "(0)"
+        if lt == "lit":
+            l = _c_lit(l)
+        if rt == "lit":
+            r = _c_lit(r)
+        return "(%s) %s (%s)" % (l, cop, r)
 
     def p_atom(self):
         t = self.take()
@@ -439,10 +549,10 @@ class Translator:
             e, et = self.p_atom()
             if t.val == "-":
                 if et == "lit":
-                    v = eval("-(%s)" % e)
-                    return (repr(float(v)) if isinstance(v, float)
-                            else repr(v)), "lit"
-                return "(-(%s))" % e, "mixed"
+                    return _lit_text(-_lit_val(e)), "lit"
+                if et == "n":
+                    return "(-(long long)(%s))" % e, "l"
+                return "(-(%s))" % e, et
             return e, et
         if t.kind == "op" and t.val == "(":
             e, et = self.p_arith()
@@ -451,7 +561,7 @@ class Translator:
                 raise ValueError("expected )")
             return "(%s)" % e, et
         if t.kind == "num":
-            return repr(t.val), "lit"
+            return _lit_text(t.val), "lit"
         if t.kind == "date":
             days = t.val
             # date +/- interval chains, folded host-side
@@ -463,7 +573,10 @@ class Translator:
                 days = _date_add(days, n if op == "+" else -n, unit)
             return repr(days), "lit"
         if t.kind == "str":
-            return t.val, "strlit"   # resolved by comparison partner
+            # a string literal is consumed by its dict-coded or raw string
+            # column partner; anywhere else it has no C form
+            raise ValueError("string literal %r needs a string column "
+                             "partner" % t.val)
         if t.kind == "ident":
             if t.val in self.schema and self.schema[t.val] == RAW_STRING:
                 if t.val in self.nullable:
@@ -548,7 +661,10 @@ class Translator:
                     cop = {"=": "==", "<>": "!="}.get(op, op)
                     raise _Folded("(%s) %s (%d)" % (ref, cop, code))
                 self.i = save
-            return ref, dtype
+            if dtype not in _TYPE_CODE:
+                raise ValueError("column %r of dtype %s has no arithmetic"
+                                 % (t.val, dtype))
+            return ref, {0: "n", 1: "d", 2: "n", 3: "l"}[_TYPE_CODE[dtype]]
         raise ValueError("unexpected token %r" % t)
 
 
@@ -629,7 +745,8 @@ class JitAggregate:
     forms the two-phase rewrite emits, sql_utils.py:299-413);
     predicate: optional filter_sql string fused into the same pass.
     run() ACCUMULATES into a DevBuffer of ngroups*naggs f64 (executor
-    state semantics, like qk_q1_agg).
+    state semantics, like qk_q1_agg). A row whose key is outside
+    [0, cardinality) contributes to no group.
 
     nullable: names of columns that may hold NULL (run() takes an
     ops.NullableColumn for each). The predicate follows SQL three-valued
@@ -662,6 +779,14 @@ class JitAggregate:
         gexpr = "0"   # [] group keys -> one grand-aggregate group
         for ref, card in gparts:
             gexpr = "(%s) * %d + (int)%s" % (gexpr, card, ref)
+        if len(gparts) > 1:
+            # a key outside [0, cardinality) would alias into another
+            # group's id: such a row gets id -1 and reaches no group, as
+            # with one key (where the id is the key itself)
+            gexpr = "(%s) ? (%s) : -1" % (
+                " && ".join("(unsigned)(%s) < %du" % (ref, card)
+                            for ref, card in gparts), gexpr)
+        self.group_expr = gexpr
         self.agg_names = []
         self.agg_ops = []            # 0=SUM, 1=MIN, 2=MAX (COUNT -> SUM 1)
         agg_exprs = []

@@ -44,6 +44,13 @@ def leaf(draw, with_is=True):
     if kind == 3:
         return ("notin", col, draw(st.lists(_num, min_size=1, max_size=4)))
     if kind == 4:
+        if draw(st.booleans()):
+            # BETWEEN whose low bound, high bound or both are columns
+            # (nullable ones included): the Kleene AND of two comparisons
+            lo = draw(st.one_of(_num, _col))
+            hi = draw(_col if not isinstance(lo, str)
+                      else st.one_of(_num, _col))
+            return ("between2", col, lo, hi)
         return ("cmp2", col, draw(_cmp), draw(_col))
     return ("isnull" if draw(st.booleans()) else "notnull", col)
 
@@ -67,6 +74,9 @@ def to_sql(p):
         return "%s %s %s" % (p[1], p[2], p[3])
     if k == "between":
         return "%s between %r and %r" % (p[1], p[2], p[3])
+    if k == "between2":
+        return "%s between %s and %s" % (
+            p[1], *[b if isinstance(b, str) else repr(b) for b in p[2:]])
     if k in ("in", "notin"):
         return "%s %sin (%s)" % (p[1], "not " if k == "notin" else "",
                                  ", ".join(repr(e) for e in p[2]))
@@ -88,6 +98,11 @@ def kleene(p, vals, valid):
     if k in ("isnull", "notnull"):
         isn = ~valid[p[1]]
         return (isn, ~isn) if k == "isnull" else (~isn, isn)
+    if k == "between2":
+        return kleene(("and", ("cmp2" if isinstance(p[2], str) else "cmp",
+                               p[1], ">=", p[2]),
+                       ("cmp2" if isinstance(p[3], str) else "cmp",
+                        p[1], "<=", p[3])), vals, valid)
     if k in ("cmp", "cmp2", "between", "in", "notin"):
         v = vals[p[1]]
         known = valid[p[1]].copy()

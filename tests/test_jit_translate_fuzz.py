@@ -3,11 +3,17 @@ predicates are rendered to SQL text, translated to C, and the C
 expression (evaluated via numpy with C semantics) must match a direct
 numpy evaluation of the predicate AST on random column data."""
 import datetime
+import os
+import sys
 
 import numpy as np
-from hypothesis import given, settings, strategies as st
+from hypothesis import assume, given, settings, strategies as st
 
 from quokka_amd import jit
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _jit_cases as T  # noqa: E402
+from _c_expr_host import CExprLib  # noqa: E402
 
 SCHEMA = {
     "a": np.dtype(np.int32),
@@ -113,6 +119,77 @@ def test_translate_matches_numpy(p):
     want = np_eval(p, cols)
     got = c_eval(expr, order, cols)
     assert np.array_equal(got, want), sql
+
+
+# ---- arithmetic productions, evaluated as C ------------------------------
+# Column arithmetic cannot be checked by eval()-ing the C text as Python
+# (`/`, literal width and int32 overflow differ), so these examples are
+# collected first, compiled once as C on the host and compared with the
+# case table's reference evaluator.
+
+def _arith(depth):
+    leaf = st.one_of(
+        st.sampled_from(list(T.GEN_SCHEMA)).map(T.C),
+        st.integers(-20, 20).map(T.L),
+        st.integers(-2000, 2000).map(lambda v: T.L(v / 100.0)))
+    if depth == 0:
+        return leaf
+    sub = _arith(depth - 1)
+    return st.one_of(
+        leaf,
+        st.tuples(st.sampled_from(list("+-*/")), sub, sub),
+        st.tuples(st.just("neg"), sub))
+
+
+@st.composite
+def arith_comparison(draw):
+    kind = draw(st.integers(0, 3))
+    x = draw(_arith(draw(st.integers(1, 3))))
+    if kind == 0:
+        return ("cmp", draw(_cmp), x, draw(_arith(1)))
+    if kind == 1:
+        return ("cmp", draw(_cmp), draw(_arith(1)), x)
+    if kind == 2:
+        return ("between", draw(_arith(1)), draw(_arith(2)), x)
+    if x[0] == "col":
+        x = ("+", x, T.L(0))
+    els = draw(st.lists(st.integers(-20, 20), min_size=1, max_size=4))
+    return (draw(st.sampled_from(["in", "notin"])), x, els)
+
+
+@st.composite
+def arith_predicate(draw, depth=0):
+    if depth >= 2 or draw(st.integers(0, 2)) == 0:
+        return draw(arith_comparison())
+    kind = draw(st.sampled_from(["and", "or", "not"]))
+    if kind == "not":
+        return ("not", draw(arith_predicate(depth=depth + 1)))
+    return (kind, draw(arith_predicate(depth=depth + 1)),
+            draw(arith_predicate(depth=depth + 1)))
+
+
+def test_translate_arithmetic_matches_reference_as_c(tmp_path):
+    cols = T.gen_data(77)
+    found = []
+
+    @settings(max_examples=200, deadline=None, database=None)
+    @given(arith_predicate())
+    def collect(p):
+        try:
+            want = T.expect_filter(p, cols)
+        except T.Unsafe:
+            assume(False)
+        expr, order = jit.translate(T.sql_of(p), T.GEN_SCHEMA)
+        assume(order)                       # literal-only: no kernel
+        found.append((T.sql_of(p), expr, order, want))
+
+    collect()
+    assert len(found) >= 100
+    lib = CExprLib([(e, [T.GEN_SCHEMA[c] for c in o]) for _, e, o, _ in found],
+                   tmp_path)
+    for i, (sql, expr, order, want) in enumerate(found):
+        got = lib.run(i, [cols[c] for c in order])
+        assert np.array_equal(got, want), (sql, expr)
 
 
 def test_translate_date_intervals_exhaustive():
