@@ -223,6 +223,29 @@ int qk_join_probe(void *stream, uint64_t n_probe, const int64_t *keys,
                   const int32_t *chain_next, uint64_t capacity, int mode,
                   uint32_t *out_probe_idx, uint32_t *out_build_idx,
                   uint64_t out_capacity, uint64_t *out_cursor_dev);
+/* The same join over a NULLABLE key column: valid_dev is the column's
+ * validity bitmap (layout under "nullable columns" below), and a NULL key
+ * matches nothing on either side, as in the reference's polars join
+ * (sql_executors.py:371). The key word under a null is never read, so it
+ * may hold anything, QK_JOIN_EMPTY included; the precondition above binds
+ * valid build keys only.
+ * Build: a null row takes no slot and no chain link but keeps its row
+ * number build_row_offset + i, so the caller still advances its build
+ * count by n_build and build indices keep addressing the payload columns.
+ * Probe: a null row is a miss decided without a walk: nothing in mode 0
+ * and 1, emitted in mode 2. Everything else as qk_join_build /
+ * qk_join_probe, which remain the entry points for columns without a
+ * bitmap. */
+int qk_join_build_valid(void *stream, uint64_t n_build, const int64_t *keys,
+                        const uint64_t *valid_dev, uint32_t build_row_offset,
+                        int64_t *slot_keys, int32_t *slot_head,
+                        int32_t *chain_next, uint64_t capacity);
+int qk_join_probe_valid(void *stream, uint64_t n_probe, const int64_t *keys,
+                        const uint64_t *valid_dev, const int64_t *slot_keys,
+                        const int32_t *slot_head, const int32_t *chain_next,
+                        uint64_t capacity, int mode, uint32_t *out_probe_idx,
+                        uint32_t *out_build_idx, uint64_t out_capacity,
+                        uint64_t *out_cursor_dev);
 
 /* ---- fused Q3 path ---------------------------------------------------- *
  * Filter + semi-join + build and filter + probe + group-by aggregate fused
@@ -514,7 +537,11 @@ int qk_pq_rle_pages(void *stream, uint64_t npages, const uint64_t *ents,
  * first, 1 = valid. The bitmap buffer is 8-byte aligned, sized up to a
  * multiple of 8 bytes plus 8 bytes of slack, and every bit at an index
  * >= n is 0 (kernels popcount whole 64-bit words without a tail mask).
- * Null join keys, null group keys and null strings are not supported.
+ * Null keys are opt-in: qk_join_build_valid / qk_join_probe_valid take a
+ * key column's bitmap, and qk_key_null_words / qk_nullword_to_valid carry
+ * null group and distinct keys through the key dictionary. Those entry
+ * points never read the value under a null. Null strings outside key
+ * columns are not supported.
  *
  * qk_pq_def_pages: definition levels of a flat column (max_def == 1, bit
  * width 1, RLE/bit-packed hybrid) -> validity bits, one wave per page.
@@ -615,6 +642,43 @@ int qk_keydict_encode(void *stream, uint64_t n, int nkeys,
 int qk_keydict_rehash(void *stream, uint32_t ncodes, int nkeys,
                       const int64_t *store, uint64_t code_cap,
                       uint64_t *slots, uint64_t capacity, uint32_t *err_dev);
+/* ---- null keys in the key dictionary ---------------------------------- *
+ * DuckDB's GROUP BY makes one group of NULL keys per null pattern and
+ * polars' unique(subset=) lets nulls equal each other. A nullable
+ * dictionary keys each row on nkeys + W words, W = ceil(nkeys / 64): the
+ * nkeys CANONICAL key words (the key word where the key is valid, 0 where
+ * it is NULL) followed by W NULL WORDS (bit k % 64 of null word k / 64 is 1
+ * when key k of the row is NULL). Two rows then share a code exactly when
+ * they have the same null pattern and equal words in every non-null
+ * position; (NULL, 0), (0, NULL), (0, 0) and (NULL, NULL) are four keys.
+ * qk_keydict_encode / qk_keydict_rehash run over the nkeys + W columns
+ * unchanged; the null words are ordinary store columns.
+ *
+ * qk_key_null_words, the prepare pass, one streaming launch:
+ * key_cols_dev: device array of nkeys pointers to i64 columns of n rows.
+ * valid_ptrs_dev: device array of nkeys bitmap pointers (layout under
+ *   "nullable columns" above; at least ceil(n / 64) whole words); 0 = key
+ *   k has no nulls, and then nothing of key k is read or written.
+ * canon_cols_dev: device array of nkeys pointers; entry k is an i64 column
+ *   of n rows wherever valid_ptrs_dev[k] != 0 and receives the canonical
+ *   copy of key k (entries of keys without a bitmap are ignored). The word
+ *   a key column holds under a null does not reach any output.
+ * null_cols_dev: device array of W pointers to i64 columns of n rows, all
+ *   written. */
+int qk_key_null_words(void *stream, uint64_t n, int nkeys,
+                      const void *key_cols_dev /* dev int64_t*[nkeys] */,
+                      const void *valid_ptrs_dev /* dev uint64_t*[nkeys] */,
+                      const void *canon_cols_dev /* dev int64_t*[nkeys] */,
+                      const void *null_cols_dev /* dev int64_t*[W] */);
+/* The inverse, at extraction: Arrow validity bitmap of one key over the
+ * first g codes, bit c = !(null_col[c] >> bit & 1), where null_col is the
+ * key's null-word store column (store + (nkeys + k / 64) * code_cap) and
+ * bit = k % 64. Writes every word of a valid_nbytes(g) = (ceil(g / 64) + 1)
+ * * 8 byte buffer (bits at an index >= g are 0, g == 0 included) and ADDS
+ * the null count to *out_null_count_dev (caller zeroes it). */
+int qk_nullword_to_valid(void *stream, uint64_t g, const int64_t *null_col,
+                         int bit, uint64_t *out_valid_dev,
+                         uint64_t *out_null_count_dev);
 /* ---- dense accumulate over key-dictionary codes ----------------------- *
  * The aggregate half of SQLAggExecutor's group-by (sql_executors.py:
  * 556-599) once qk_keydict_encode has turned the key columns into dense

@@ -1132,6 +1132,110 @@ extern "C" int qk_join_probe(void *stream, uint64_t n, const int64_t *keys,
   return 0;
 }
 
+// ---- join over a nullable key column -----------------------------------
+// SQL: a NULL key equals nothing, on either side (polars join,
+// sql_executors.py:371). `valid` is the key column's Arrow validity bitmap
+// (include/quokka_amd.h, nullable columns); whatever the key column holds
+// under a null is never read. k_join_build2 and k_join_probe above stay
+// the kernels of the no-bitmap entry points.
+__device__ inline bool qk_valid_bit(const uint8_t *__restrict__ valid,
+                                    uint64_t i) {
+  return (valid[i >> 3] >> (i & 7)) & 1;
+}
+
+// A null build row takes no slot and no chain link but keeps its row
+// number, so build indices still address the payload columns.
+__global__ void __launch_bounds__(BLOCK) k_join_build_valid(
+    uint64_t n, const int64_t *__restrict__ keys,
+    const uint8_t *__restrict__ valid, uint32_t row_offset,
+    int64_t *__restrict__ slot_keys, int32_t *__restrict__ slot_head,
+    int32_t *__restrict__ chain_next, uint64_t cap) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    if (!qk_valid_bit(valid, i)) continue;
+    uint64_t s = ht_find_or_insert(slot_keys, cap, keys[i]);
+    int32_t me = (int32_t)(row_offset + i);
+    int32_t old = atomicExch(&slot_head[s], me);
+    chain_next[me] = old;
+  }
+}
+
+extern "C" int qk_join_build_valid(void *stream, uint64_t n,
+                                   const int64_t *keys,
+                                   const uint64_t *valid_dev,
+                                   uint32_t row_offset, int64_t *slot_keys,
+                                   int32_t *slot_head, int32_t *chain_next,
+                                   uint64_t cap) {
+  if (!n) return 0;
+  if (!qk_pow2(cap))
+    return qk_fail("qk_join_build_valid.cap_pow2", hipErrorInvalidValue);
+  if (!valid_dev)
+    return qk_fail("qk_join_build_valid.valid_null", hipErrorInvalidValue);
+  hipLaunchKernelGGL(k_join_build_valid, dim3(qk_grid(n)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, n, keys, (const uint8_t *)valid_dev,
+                     row_offset, slot_keys, slot_head, chain_next, cap);
+  QK_TRY("qk_join_build_valid", hipGetLastError());
+  return 0;
+}
+
+// A null probe row is a miss without a walk: nothing for inner and semi,
+// emitted for anti.
+__global__ void __launch_bounds__(BLOCK) k_join_probe_valid(
+    uint64_t n, const int64_t *__restrict__ keys,
+    const uint8_t *__restrict__ valid,
+    const int64_t *__restrict__ slot_keys, const int32_t *__restrict__ slot_head,
+    const int32_t *__restrict__ chain_next, uint64_t cap, int mode,
+    uint32_t *__restrict__ out_probe, uint32_t *__restrict__ out_build,
+    uint64_t out_cap, uint64_t *__restrict__ cursor) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    int32_t head = -1;
+    if (qk_valid_bit(valid, i))
+      head = probe_unique(slot_keys, slot_head, cap, keys[i], nullptr);
+    if (mode != 0) {  // semi emits hits, anti emits misses
+      if ((head >= 0) == (mode == 1)) {
+        uint64_t pos = atomicAdd((unsigned long long *)cursor, 1ULL);
+        if (pos < out_cap) out_probe[pos] = (uint32_t)i;
+      }
+      continue;
+    }
+    if (head < 0) continue;
+    uint32_t cnt = 0;
+    for (int32_t b = head; b >= 0; b = chain_next[b]) cnt++;
+    uint64_t pos = atomicAdd((unsigned long long *)cursor, (unsigned long long)cnt);
+    for (int32_t b = head; b >= 0; b = chain_next[b]) {
+      if (pos < out_cap) {
+        out_probe[pos] = (uint32_t)i;
+        out_build[pos] = (uint32_t)b;
+      }
+      pos++;
+    }
+  }
+}
+extern "C" int qk_join_probe_valid(void *stream, uint64_t n,
+                                   const int64_t *keys,
+                                   const uint64_t *valid_dev,
+                                   const int64_t *slot_keys,
+                                   const int32_t *slot_head,
+                                   const int32_t *chain_next, uint64_t cap,
+                                   int mode, uint32_t *out_probe,
+                                   uint32_t *out_build, uint64_t out_cap,
+                                   uint64_t *cursor) {
+  if (!n) return 0;
+  if (!qk_pow2(cap))
+    return qk_fail("qk_join_probe_valid.cap_pow2", hipErrorInvalidValue);
+  if (!valid_dev || mode < 0 || mode > 2 || (mode == 0 && !out_build))
+    return qk_fail("qk_join_probe_valid.args", hipErrorInvalidValue);
+  hipLaunchKernelGGL(k_join_probe_valid, dim3(qk_grid(n)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, n, keys, (const uint8_t *)valid_dev,
+                     slot_keys, slot_head, chain_next, cap, mode, out_probe,
+                     out_build, out_cap, cursor);
+  QK_TRY("qk_join_probe_valid", hipGetLastError());
+  return 0;
+}
+
 // ---- fused Q3 path -----------------------------------------------------
 // Build/probe with the surrounding filter and aggregate FUSED into the
 // table pass (the reference folds the filter and per-batch partial agg
@@ -3174,6 +3278,100 @@ extern "C" int qk_keydict_rehash(void *stream, uint32_t ncodes, int nkeys,
                      (hipStream_t)stream, ncodes, nkeys, store, code_cap,
                      slots, cap, err_dev);
   QK_TRY("qk_keydict_rehash", hipGetLastError());
+  return 0;
+}
+
+// ---- null keys: K key words + W = ceil(K / 64) null words per row ------
+// DuckDB's GROUP BY puts NULL keys in one group per null pattern and
+// polars' unique(subset=) lets nulls equal each other (sql_executors.py:
+// 556-599, :517-554). A nullable dictionary therefore keys rows on the K
+// canonical words (0 where the key is NULL) followed by W null words (bit
+// k % 64 of word k / 64 set when key k is NULL), and the claim / finalise
+// / resolve / rehash kernels above run over K + W pointers unchanged.
+//
+// The prepare pass is a stream: a wave covers 64 consecutive rows (BLOCK
+// and the grid stride are multiples of 64), so a key's validity word is
+// one load of the same address for the whole wave and each lane tests its
+// own bit. valid[k] == 0 means key k has no nulls: its bitmap is not
+// read, it gets no canonical copy, and it sets no null bit.
+__global__ void __launch_bounds__(BLOCK) k_key_null_words(
+    uint64_t n, int nkeys, const int64_t *const *__restrict__ cols,
+    const uint64_t *const *__restrict__ valid,
+    int64_t *const *__restrict__ canon, int64_t *const *__restrict__ nullw) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  uint32_t lane = threadIdx.x & (WAVE - 1);
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    uint64_t nw = 0;
+    for (int k = 0; k < nkeys; k++) {
+      const uint64_t *vp = valid[k];
+      if (vp) {
+        bool ok = (vp[i >> 6] >> lane) & 1;
+        canon[k][i] = ok ? cols[k][i] : 0;
+        if (!ok) nw |= 1ULL << (k & 63);
+      }
+      if ((k & 63) == 63 || k == nkeys - 1) {
+        nullw[k >> 6][i] = (int64_t)nw;
+        nw = 0;
+      }
+    }
+  }
+}
+extern "C" int qk_key_null_words(void *stream, uint64_t n, int nkeys,
+                                 const void *key_cols_dev,
+                                 const void *valid_ptrs_dev,
+                                 const void *canon_cols_dev,
+                                 const void *null_cols_dev) {
+  if (!n) return 0;
+  if (nkeys < 1 || !key_cols_dev || !valid_ptrs_dev || !canon_cols_dev ||
+      !null_cols_dev)
+    return qk_fail("qk_key_null_words.args", hipErrorInvalidValue);
+  hipLaunchKernelGGL(k_key_null_words, dim3(qk_grid(n)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, n, nkeys,
+                     (const int64_t *const *)key_cols_dev,
+                     (const uint64_t *const *)valid_ptrs_dev,
+                     (int64_t *const *)canon_cols_dev,
+                     (int64_t *const *)null_cols_dev);
+  QK_TRY("qk_key_null_words", hipGetLastError());
+  return 0;
+}
+
+// The inverse, at extraction: validity bitmap of one key over the first g
+// codes from its null-word store column. Every wave step packs 64 bits
+// with __ballot and lane 0 stores the word; the loop runs on the wave's
+// first index so that all 64 lanes reach the ballot, and it covers every
+// word of a valid_nbytes(g) buffer, the slack word included.
+__global__ void __launch_bounds__(BLOCK) k_nullword_to_valid(
+    uint64_t g, uint64_t nwords, const int64_t *__restrict__ null_col, int bit,
+    uint64_t *__restrict__ out_valid, uint64_t *__restrict__ null_count) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  uint32_t lane = threadIdx.x & (WAVE - 1);
+  uint32_t nulls = 0;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x - lane;
+       i0 < nwords * WAVE; i0 += stride) {
+    uint64_t i = i0 + lane;
+    bool ok = false;
+    if (i < g) {
+      ok = !(((uint64_t)null_col[i] >> bit) & 1);
+      nulls += ok ? 0u : 1u;
+    }
+    uint64_t m = __ballot(ok);
+    if (lane == 0) out_valid[i0 >> 6] = m;
+  }
+  block_add_count(nulls, null_count);
+}
+extern "C" int qk_nullword_to_valid(void *stream, uint64_t g,
+                                    const int64_t *null_col, int bit,
+                                    uint64_t *out_valid_dev,
+                                    uint64_t *out_null_count_dev) {
+  if (bit < 0 || bit > 63 || !out_valid_dev || !out_null_count_dev ||
+      (g && !null_col))
+    return qk_fail("qk_nullword_to_valid.args", hipErrorInvalidValue);
+  uint64_t nwords = (g + 63) / 64 + 1;
+  hipLaunchKernelGGL(k_nullword_to_valid, dim3(qk_grid(nwords * WAVE)),
+                     dim3(BLOCK), 0, (hipStream_t)stream, g, nwords, null_col,
+                     bit, out_valid_dev, out_null_count_dev);
+  QK_TRY("qk_nullword_to_valid", hipGetLastError());
   return 0;
 }
 

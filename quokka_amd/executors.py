@@ -67,10 +67,16 @@ class GPUBuildProbeJoinExecutor(Executor):
     column like :372-373. Differences documented in DESIGN.md: the build
     state is a device hash table (the reference's vstack+sort+polars-join is
     an implementation detail, :358/:369); result row ORDER within a batch is
-    unspecified (as is polars'). i64 keys supported."""
+    unspecified (as is polars'). i64 keys supported.
+
+    null_keys=True admits NULL join keys, int or string, on both sides: a
+    NULL matches nothing, as in polars, so inner and semi drop such rows
+    and left and anti keep the probe's, with the key column still in its
+    type and NULL (DESIGN.md §3a'''). The default refuses or mangles them
+    as before."""
 
     def __init__(self, on=None, left_on=None, right_on=None, how="inner",
-                 key_to_keep="left"):
+                 key_to_keep="left", null_keys=False):
         if on is not None:
             if left_on is not None or right_on is not None:
                 raise ValueError("pass either on= or left_on=/right_on=, "
@@ -88,6 +94,8 @@ class GPUBuildProbeJoinExecutor(Executor):
                              "anti, as the reference)" % (how,))
         self.how = how
         self.key_to_keep = key_to_keep
+        self.null_keys = bool(null_keys)
+        self._build_key_masks = []  # null_keys: one bool mask per batch
         self.phase = "build"
         # lazy GPU state (created on first execute, never in __init__)
         self._table = None
@@ -121,6 +129,14 @@ class GPUBuildProbeJoinExecutor(Executor):
                     # KEYS go through the device string dictionary,
                     # payloads are host-gathered at emit
                     self._build_cols[c].append(col)
+                elif self.null_keys and c == self.right_on:
+                    # the key's mask travels beside its values, so an int
+                    # key with nulls stays int
+                    mask = np.ones(len(col), dtype=bool)
+                    if col.null_count:
+                        col, mask = staging.split_nulls(col)
+                    self._build_cols[c].append(staging.column_to_numpy(col))
+                    self._build_key_masks.append(mask)
                 else:
                     self._build_cols[c].append(
                         staging.column_to_numpy(col))
@@ -136,10 +152,22 @@ class GPUBuildProbeJoinExecutor(Executor):
         self.phase = "probe"
         return self._probe(batch)
 
+    def _encode_string_keys(self, col):
+        """String key column -> (i64 dictionary codes, bool mask or None).
+        Without null_keys nulls raise, as before."""
+        if not self.null_keys:
+            return self._key_dict.encode_column(col).astype(np.int64), None
+        codes, mask = self._key_dict.encode_column(col, nulls="mask")
+        return codes.astype(np.int64), mask
+
     def _finish_build(self):
         ops, shim, staging = _lazy_gpu()
         self._host_build = {}
         self._build_payload_host = {}     # string payloads, host-gathered
+        kmask = None                      # null_keys: validity of the keys
+        if self._build_key_masks:
+            kmask = np.concatenate(self._build_key_masks)
+            self._build_key_masks = []
         for c, v in self._build_cols.items():
             if v and not isinstance(v[0], np.ndarray):
                 col = _concat_col(v)
@@ -149,8 +177,8 @@ class GPUBuildProbeJoinExecutor(Executor):
                     # equal strings get equal codes (bytes verified)
                     self._key_dict = ops.DeviceStringDict(
                         expected=max(1024, col.length()))
-                    self._host_build[c] = self._key_dict.encode_column(
-                        col).astype(np.int64)
+                    self._host_build[c], kmask = \
+                        self._encode_string_keys(col)
                 else:
                     self._build_payload_host[c] = np.asarray(
                         col.to_pylist(), dtype=object)
@@ -161,9 +189,9 @@ class GPUBuildProbeJoinExecutor(Executor):
                     if c == self.right_on:
                         self._key_dict = ops.DeviceStringDict(
                             expected=max(1024, len(arr)))
-                        self._host_build[c] = self._key_dict.encode_column(
-                            pa.chunked_array([pa.array(arr)])
-                        ).astype(np.int64)
+                        self._host_build[c], kmask = \
+                            self._encode_string_keys(
+                                pa.chunked_array([pa.array(arr)]))
                     else:
                         self._build_payload_host[c] = arr
                 else:
@@ -175,14 +203,20 @@ class GPUBuildProbeJoinExecutor(Executor):
             else:
                 raise TypeError("GPU join requires integer or string keys,"
                                 " got %s" % keys.dtype)
+        if kmask is not None and kmask.all():
+            kmask = None
         if self._key_dict is None:      # dictionary codes are >= 0
-            ops.check_no_sentinel_key(keys, type(self).__name__,
-                                      self.right_on)
+            ops.check_no_sentinel_key(
+                keys if kmask is None else keys[kmask],
+                type(self).__name__, self.right_on)
         n = len(keys)
         self._table = ops.JoinTable(max(16, n))
         if n:
             kcol = shim.DevColumn.from_numpy(keys)
-            self._table.build(kcol)
+            if kmask is None:
+                self._table.build(kcol)
+            else:
+                self._table.build(kcol, valid=kmask)
             kcol.free()
         self._build_payload_dev = {}
         for c in self._build_names:
@@ -195,14 +229,18 @@ class GPUBuildProbeJoinExecutor(Executor):
     def _probe(self, batch):
         ops, shim, staging = _lazy_gpu()
         key_col = batch.column(self.left_on)
+        pmask = None            # null_keys: validity of the probe keys
+        key_vals = None         # ... and the numeric key, 0 under nulls
         if _is_stringish(key_col):
             if self._key_dict is None:
                 raise TypeError("string probe keys against a non-string "
                                 "build side")
             # same device dictionary as the build side: equal strings ==
             # equal codes (bytes verified in-kernel)
-            probe_keys = self._key_dict.encode_column(
-                key_col).astype(np.int64)
+            probe_keys, pmask = self._encode_string_keys(key_col)
+        elif self.null_keys and key_col.null_count:
+            filled, pmask = staging.split_nulls(key_col)
+            probe_keys = key_vals = staging.column_to_numpy(filled)
         else:
             probe_keys = staging.column_to_numpy(key_col)
         if probe_keys.dtype != np.int64:
@@ -213,7 +251,10 @@ class GPUBuildProbeJoinExecutor(Executor):
                                 " got %s" % probe_keys.dtype)
         kcol = shim.DevColumn.from_numpy(probe_keys)
         mode = {"inner": 0, "left": 0, "semi": 1, "anti": 2}[self.how]
-        pidx, bidx, nm = self._table.probe(kcol, mode=mode)
+        if pmask is None:
+            pidx, bidx, nm = self._table.probe(kcol, mode=mode)
+        else:
+            pidx, bidx, nm = self._table.probe(kcol, mode=mode, valid=pmask)
 
         def dev_gather(host_arr, idx_col):
             """stage -> device gather by idx -> one DMA into a PINNED
@@ -243,9 +284,30 @@ class GPUBuildProbeJoinExecutor(Executor):
             host-side (emit is host Arrow anyway), numerics through the
             device gather like the reference's polars emit."""
             col = batch.column(c)
+            if c == self.left_on and pmask is not None:
+                return null_key_rows(col, rows_dev, rows_host)
             if _is_stringish(col):
                 return np.asarray(col.to_pylist(), dtype=object)[rows_host]
             return dev_gather(staging.column_to_numpy(col), rows_dev)
+
+        def null_key_rows(col, rows_dev, rows_host):
+            """The key column when it holds nulls (null_keys=True): type
+            and nulls kept. Only anti emits null-key rows from the device
+            indices; inner, semi and the matched part of left select none,
+            so the filled values are gathered as any numeric column."""
+            import pyarrow as pa
+            if key_vals is None:        # string key: Arrow take on the host
+                return col.combine_chunks().take(
+                    pa.array(rows_host, type=pa.int64()))
+            if self.how != "anti" or not nm:
+                return dev_gather(key_vals, rows_dev)
+            from . import bridge
+            src = ops.NullableColumn.from_numpy(key_vals, pmask)
+            g = ops.take_nullable(src, rows_dev, nm)
+            res = bridge.column_to_arrow(g)
+            src.free()
+            g.free()
+            return res
 
         out = {}
         if self.how in ("semi", "anti"):
@@ -271,6 +333,18 @@ class GPUBuildProbeJoinExecutor(Executor):
                     import pyarrow as pa
                     for c in batch.column_names:
                         col = batch.column(c)
+                        if c == self.left_on and pmask is not None:
+                            # unmatched rows include every null-key row
+                            if key_vals is None:
+                                tail = col.combine_chunks().take(
+                                    pa.array(un, type=pa.int64()))
+                                head = out[c]
+                            else:
+                                tail = pa.array(key_vals[un],
+                                                mask=~pmask[un])
+                                head = pa.array(out[c])
+                            out[c] = pa.concat_arrays([head, tail])
+                            continue
                         if _is_stringish(col):
                             tailv = np.asarray(col.to_pylist(),
                                                dtype=object)[un]
@@ -365,10 +439,15 @@ class _KeyWords:
     64-bit words (one np.int64 array per key) and back: the Arrow type of
     each key from the first batch, and one DeviceStringDict per string
     key. Numeric, bool and date/time keys convert on the host through
-    key_to_words; a string key's word is its dictionary code."""
+    key_to_words; a string key's word is its dictionary code.
 
-    def __init__(self, names):
+    null_keys=True admits NULL keys: words() then also returns one host
+    bool mask (True = valid) or None per key, the word under a null is 0,
+    and decode() / to_arrow() take the mask back."""
+
+    def __init__(self, names, null_keys=False):
         self.names = list(names)
+        self.null_keys = bool(null_keys)
         self.types = {}
         self.dicts = {}
 
@@ -394,32 +473,72 @@ class _KeyWords:
 
     def check(self, batch, who):
         """Host-only: refuse null keys before any device work."""
+        if self.null_keys:
+            return
         for k in self.names:
             if batch.column(k).null_count:
                 raise TypeError(
                     "%s: key column %r has nulls; null keys are not "
                     "supported (DESIGN.md §3a')" % (who, k))
 
+    @staticmethod
+    def _split_nulls(col):
+        """Arrow key column with nulls -> (the column with its null slots
+        filled with 0, host bool mask). staging.split_nulls for numeric,
+        bool and date32 keys, so ints stay ints; the other temporal types,
+        which it refuses, through their integer storage here."""
+        import pyarrow as pa
+        import pyarrow.compute as pc
+        from . import staging
+        if isinstance(col, pa.ChunkedArray):
+            col = col.combine_chunks()
+        t = col.type
+        if pa.types.is_temporal(t) and not pa.types.is_date32(t):
+            mask = pc.is_valid(col).to_numpy(zero_copy_only=False)
+            store = pa.int32() if pa.types.is_time32(t) else pa.int64()
+            return (col.cast(store).fill_null(0),
+                    np.ascontiguousarray(mask, dtype=bool))
+        return staging.split_nulls(col)
+
     def words(self, batch, ops):
-        outs = []
+        """-> one np.int64 word array per key; with null_keys=True
+        (words, masks), masks[k] a host bool array or None."""
+        outs, masks = [], []
         for k in self.names:
             col = batch.column(k)
             self.types.setdefault(k, col.type)
+            mask = None
             if _is_stringish(col):
                 sd = self.dicts.get(k)
                 if sd is None:
                     sd = self.dicts[k] = ops.DeviceStringDict(expected=4096)
-                outs.append(sd.encode_column(col).astype(np.int64))
+                if self.null_keys:
+                    codes, mask = sd.encode_column(col, nulls="mask")
+                    w = codes.astype(np.int64)
+                    if mask is not None:
+                        w[~mask] = 0
+                    outs.append(w)
+                else:
+                    outs.append(sd.encode_column(col).astype(np.int64))
+            elif self.null_keys and col.null_count:
+                filled, mask = self._split_nulls(col)
+                outs.append(key_to_words(self._storage(filled)))
             else:
                 outs.append(key_to_words(self._storage(col)))
-        return outs
+            masks.append(mask)
+        return (outs, masks) if self.null_keys else outs
 
-    def decode(self, name, words):
+    def decode(self, name, words, mask=None):
         """words -> numpy values that sort like the column (strings as an
-        object array, dates as their integer count)."""
+        object array, dates as their integer count). With a mask, string
+        rows that are NULL come back as '' (their word is no code)."""
         import pyarrow as pa
         t = self.types[name]
         sd = self.dicts.get(name)
+        if sd is not None and mask is not None:
+            out = np.full(len(words), "", dtype=object)
+            out[mask] = sd.decode(np.asarray(words)[mask])
+            return out
         if sd is not None:
             return sd.decode(words)
         if pa.types.is_date32(t) or pa.types.is_time32(t):
@@ -428,12 +547,20 @@ class _KeyWords:
             return words_to_key(words, np.int64)
         return words_to_key(words, t.to_pandas_dtype())
 
-    def to_arrow(self, name, values):
-        """decode()'s values -> Arrow array of the key's original type."""
+    def to_arrow(self, name, values, mask=None):
+        """decode()'s values -> Arrow array of the key's original type (a
+        dictionary-encoded key comes back in its value type); rows where
+        `mask` is False are NULL."""
         import pyarrow as pa
         t = self.types[name]
         if pa.types.is_dictionary(t):
             t = t.value_type
+        if mask is not None:
+            nulls = ~np.asarray(mask, dtype=bool)
+            if name in self.dicts:
+                return pa.array(np.asarray(values, dtype=object), type=t,
+                                mask=nulls)
+            return pa.array(np.asarray(values), mask=nulls).cast(t)
         if name in self.dicts:
             return pa.array(values, type=t)
         return pa.array(values).cast(t)
@@ -466,17 +593,27 @@ class GPUAggExecutor(Executor):
     §3a''): any number of keys, int / bool / date / float / string, up to
     2**31 - 1 groups, key columns returned in their original Arrow types.
     Null keys raise TypeError. The default is the composite path, as before.
-    """
+
+    null_keys=True (with device_keys=True) makes NULL a group, one per
+    null pattern across the keys, as DuckDB's GROUP BY does: done() returns
+    the key columns in their Arrow types with the nulls in place, and an
+    order-by over such a key puts its NULLs last in both directions
+    (DESIGN.md §3a'''). Nulls in the aggregated value columns stay
+    unsupported."""
 
     def __init__(self, groupby_keys, orderby_keys, sql_statement,
-                 device_keys=False):
+                 device_keys=False, null_keys=False):
         if not isinstance(groupby_keys, list):
             raise TypeError("groupby_keys must be a list (may be empty "
                             "for a grand aggregate)")
+        if null_keys and not device_keys:
+            raise ValueError("null_keys=True needs device_keys=True: the "
+                             "composite key encoding has no place for NULL")
         self.groupby_keys = groupby_keys
         self.orderby_keys = orderby_keys or []
         self.sql_statement = sql_statement
         self.device_keys = bool(device_keys)
+        self.null_keys = bool(null_keys)
         self.sum_cols = []          # partial columns referenced by aggs
         self.agg_ops = []           # per column: 0 SUM / 1 MIN / 2 MAX
         self.exprs = []             # (alias, python expr over s['col'])
@@ -650,20 +787,23 @@ class GPUAggExecutor(Executor):
         number of keys, any cardinality up to 2**31 - 1 groups."""
         ops, shim, staging = _lazy_gpu()
         if self._key_words is None:
-            self._key_words = _KeyWords(self.groupby_keys)
+            self._key_words = _KeyWords(self.groupby_keys, self.null_keys)
         self._key_words.check(batch, type(self).__name__)
-        words = self._key_words.words(batch, ops)
+        words, masks = self._key_words.words(batch, ops), None
+        if self.null_keys:
+            words, masks = words
         if self._gb is None:
             self._gb = ops.GroupByKeys(
                 len(self.groupby_keys), len(self.sum_cols),
                 agg_ops=self.agg_ops,
-                expected_groups=max(1024, len(batch)))
+                expected_groups=max(1024, len(batch)),
+                nullable_keys=self.null_keys)
         kcols = [shim.DevColumn.from_numpy(w) for w in words]
         vcols = [shim.DevColumn.from_numpy(
             staging.column_to_numpy(batch.column(c)).astype(np.float64))
             for c in self.sum_cols]
         try:
-            self._gb.update(kcols, vcols, len(batch))
+            self._gb.update(kcols, vcols, len(batch), key_valid=masks)
         finally:
             for c in kcols + vcols:
                 c.free()
@@ -672,27 +812,34 @@ class GPUAggExecutor(Executor):
         key_words, sums = self._gb.extract()
         s = {c: sums[i] for i, c in enumerate(self.sum_cols)}
         kw = self._key_words
-        out = {k: kw.decode(k, w)
+        masks = {}
+        if self.null_keys:
+            masks = dict(zip(self.groupby_keys, self._gb.extract_valid()))
+        out = {k: kw.decode(k, w, masks.get(k))
                for k, w in zip(self.groupby_keys, key_words)}
         for alias, expr in self.exprs:
             out[alias] = eval(expr, {"s": s})  # noqa: S307 — expr built above
         # bool keys order as 0/1 (numpy refuses to negate a bool array)
         order = self._order_by({k: (v.astype(np.uint8)
                                     if getattr(v, "dtype", None) == np.bool_
-                                    else v) for k, v in out.items()})
+                                    else v) for k, v in out.items()},
+                               masks)
         if order is not None:
             out = {k: np.asarray(v)[order] for k, v in out.items()}
+            masks = {k: m[order] for k, m in masks.items()}
         for k in self.groupby_keys:
-            out[k] = kw.to_arrow(k, out[k])
+            out[k] = kw.to_arrow(k, out[k], masks.get(k))
         self._gb.free()
         self._gb = None
         kw.free()
         self._key_words = None
         return _to_table(out)
 
-    def _order_by(self, out):
+    def _order_by(self, out, masks=None):
         """Row order of the order-by clause over the output columns, or
-        None without one."""
+        None without one. masks: key -> bool array (True = valid) of the
+        null_keys path; the NULLs of such a key sort last, ascending and
+        descending alike."""
         if not self.orderby_keys:
             return None
         cols = []
@@ -708,6 +855,10 @@ class GPUAggExecutor(Executor):
                     _, inv = np.unique(v, return_inverse=True)
                     v = inv.max() - inv
             cols.append(v)
+            if masks and k in masks:
+                # more significant than the key's own value, less than
+                # the order-by keys before it
+                cols.append(~masks[k])
         return np.lexsort(cols)
 
     def done(self, executor_id):
@@ -759,11 +910,12 @@ class GPUBroadcastJoinExecutor(GPUBuildProbeJoinExecutor):
     the table is built lazily from the stored host columns."""
 
     def __init__(self, small_table, on=None, small_on=None, big_on=None,
-                 suffix="_small", how="inner"):
+                 suffix="_small", how="inner", null_keys=False):
         if on is not None:
             assert small_on is None and big_on is None
             small_on = big_on = on
-        super().__init__(left_on=big_on, right_on=small_on, how=how)
+        super().__init__(left_on=big_on, right_on=small_on, how=how,
+                         null_keys=null_keys)
         self.suffix = suffix
         import pyarrow as pa
         if not isinstance(small_table, pa.Table):
@@ -771,6 +923,15 @@ class GPUBroadcastJoinExecutor(GPUBuildProbeJoinExecutor):
         self._small_host = {c: small_table.column(c).to_numpy(
             zero_copy_only=False) for c in small_table.column_names}
         assert self.right_on in self._small_host
+        self._small_key_mask = None
+        key = small_table.column(self.right_on)
+        if self.null_keys and key.null_count and not _is_stringish(key):
+            # a numeric key keeps its mask beside 0-filled values (a null
+            # string key stays None in the object array and is masked
+            # when _finish_build encodes it)
+            from . import staging
+            filled, self._small_key_mask = staging.split_nulls(key)
+            self._small_host[self.right_on] = staging.column_to_numpy(filled)
 
     def execute(self, batches, stream_id, executor_id):
         import pyarrow as pa
@@ -781,6 +942,8 @@ class GPUBroadcastJoinExecutor(GPUBuildProbeJoinExecutor):
             self._build_names = list(self._small_host.keys())
             self._build_cols = {c: [np.asarray(v)]
                                 for c, v in self._small_host.items()}
+            if self._small_key_mask is not None:
+                self._build_key_masks = [self._small_key_mask]
             self._finish_build()
         self.phase = "probe"
         return self._probe(pa.concat_tables(batches))
@@ -927,10 +1090,18 @@ class GPUDistinctExecutor(Executor):
 
     `keys` as a str or a one-element list is that single-column path. A
     list of two or more columns is the reference's unique(subset=keys)
-    over all of them, through ops.DeviceKeyDict (DESIGN.md §3a'')."""
+    over all of them, through ops.DeviceKeyDict (DESIGN.md §3a'').
 
-    def __init__(self, keys):
-        self._multi = not isinstance(keys, str) and len(keys) >= 2
+    null_keys=True admits NULL keys, which equal each other as in polars'
+    unique: every form, the single key included, then goes through a
+    nullable DeviceKeyDict (DESIGN.md §3a''')."""
+
+    def __init__(self, keys, null_keys=False):
+        self.null_keys = bool(null_keys)
+        if self.null_keys and isinstance(keys, str):
+            keys = [keys]
+        self._multi = not isinstance(keys, str) and \
+            (len(keys) >= 2 or (self.null_keys and len(keys) == 1))
         if self._multi:
             # unique(subset=keys) over two or more columns: every row's
             # key tuple -> one dense code (ops.DeviceKeyDict)
@@ -958,16 +1129,19 @@ class GPUDistinctExecutor(Executor):
         the batch, first occurrence of that code."""
         ops, shim, staging = _lazy_gpu()
         if self._key_words is None:
-            self._key_words = _KeyWords(self.keys)
+            self._key_words = _KeyWords(self.keys, self.null_keys)
         self._key_words.check(batch, type(self).__name__)
-        words = self._key_words.words(batch, ops)
+        words, masks = self._key_words.words(batch, ops), None
+        if self.null_keys:
+            words, masks = words
         if self._kd is None:
             self._kd = ops.DeviceKeyDict(len(self.keys),
-                                         expected=max(1024, len(batch)))
+                                         expected=max(1024, len(batch)),
+                                         nullable=self.null_keys)
         before = self._kd.n_codes
         kcols = [shim.DevColumn.from_numpy(w) for w in words]
         try:
-            dcodes = self._kd.encode(kcols, len(batch))
+            dcodes = self._kd.encode(kcols, len(batch), valid=masks)
         finally:
             for c in kcols:
                 c.free()

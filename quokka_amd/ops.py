@@ -104,6 +104,28 @@ def _pow2_at_least(n):
     return c
 
 
+def _key_bitmap(col, valid, n):
+    """Validity bitmap of a key column for n rows -> (device bitmap or
+    None, owned). `valid` is None, a device bitmap (anything with .ptr, in
+    the NullableColumn.valid layout) or a host bool mask (True = valid),
+    which is packed and uploaded; with None a NullableColumn supplies its
+    own. The caller frees an owned bitmap."""
+    if valid is None:
+        return (col.valid, False) if isinstance(col, NullableColumn) \
+            else (None, False)
+    if hasattr(valid, "ptr"):
+        return valid, False
+    mask = np.asarray(valid)
+    if mask.dtype != np.bool_ or mask.ndim != 1 or len(mask) < n:
+        raise TypeError("key validity: a device bitmap or a host bool "
+                        "mask of at least n rows expected")
+    bits = pack_valid(mask[:n])
+    buf = DevBuffer(len(bits))
+    shim.call("qk_h2d", buf.ptr, bits.ctypes.data_as(c_vp),
+              c_u64(len(bits)))
+    return buf, True
+
+
 class JoinTable:
     """Device hash-join state = BuildProbeJoinExecutor's vstacked build side
     (sql_executors.py:346-374). build() may be called per build batch;
@@ -112,7 +134,14 @@ class JoinTable:
     Precondition: no BUILD key equals INT64_MIN (QK_JOIN_EMPTY, the
     free-slot marker). build() takes device keys and does not look at
     them; callers with host keys use check_no_sentinel_key first. Probe
-    keys may take any value."""
+    keys may take any value.
+
+    Null keys: build() and probe() take `valid`, the key column's validity
+    (a device bitmap or a host bool mask; a NullableColumn supplies its
+    own). A null key matches nothing on either side and the word under it
+    is never read, so the precondition binds valid build keys only. A null
+    build row still takes its row number, so build indices address the
+    payload columns as before."""
 
     def __init__(self, expected_build_rows, stream=None):
         self.cap = _pow2_at_least(max(16, 2 * int(expected_build_rows)))
@@ -128,7 +157,7 @@ class JoinTable:
         shim.call("qk_dmemset", self.slot_head.ptr, 0xFF,
                   c_u64(self.cap * 4))
 
-    def build(self, keys_col, n=None):
+    def build(self, keys_col, n=None, valid=None):
         n = keys_col.n if n is None else n
         if self.n_build + n > self.chain_cap or self.n_build + n > self.cap // 2:
             raise RuntimeError(
@@ -136,33 +165,54 @@ class JoinTable:
                 "table from the build side's total rows"
                 % (self.n_build, n, min(self.chain_cap, self.cap // 2)))
         sh = self.stream.handle if self.stream else None
-        shim.call("qk_join_build", sh, c_u64(n), keys_col.ptr,
-                  c_u32(self.n_build), self.slot_keys.ptr,
-                  self.slot_head.ptr, self.chain_next.ptr, c_u64(self.cap))
+        bitmap, owned = _key_bitmap(keys_col, valid, n)
+        if bitmap is None:
+            shim.call("qk_join_build", sh, c_u64(n), keys_col.ptr,
+                      c_u32(self.n_build), self.slot_keys.ptr,
+                      self.slot_head.ptr, self.chain_next.ptr,
+                      c_u64(self.cap))
+        else:
+            shim.call("qk_join_build_valid", sh, c_u64(n), keys_col.ptr,
+                      bitmap.ptr, c_u32(self.n_build), self.slot_keys.ptr,
+                      self.slot_head.ptr, self.chain_next.ptr,
+                      c_u64(self.cap))
+            if owned:
+                shim.call("qk_stream_sync", sh)
+                bitmap.free()
         self.n_build += n
 
-    def probe(self, keys_col, mode=0, out_factor=1.5, n=None):
+    def probe(self, keys_col, mode=0, out_factor=1.5, n=None, valid=None):
         """mode 0 inner / 1 semi / 2 anti. Returns (probe_idx, build_idx,
         count) DevColumns (build_idx None for semi/anti). Grows the output
         and re-probes when the first guess undershoots (counted, never
-        truncated)."""
+        truncated). With `valid` a null probe row is a miss."""
         n = keys_col.n if n is None else n
         sh = self.stream.handle if self.stream else None
+        bitmap, owned = _key_bitmap(keys_col, valid, n)
         out_cap = max(16, int(n * out_factor))
         while True:
             probe_idx = DevColumn(np.uint32, out_cap)
             build_idx = DevColumn(np.uint32, out_cap) if mode == 0 else None
             cur = _count_buf()
-            shim.call("qk_join_probe", sh, c_u64(n), keys_col.ptr,
-                      self.slot_keys.ptr, self.slot_head.ptr,
-                      self.chain_next.ptr, c_u64(self.cap), mode,
-                      probe_idx.ptr, build_idx.ptr if build_idx else None,
-                      c_u64(out_cap), cur.ptr)
+            if bitmap is None:
+                shim.call("qk_join_probe", sh, c_u64(n), keys_col.ptr,
+                          self.slot_keys.ptr, self.slot_head.ptr,
+                          self.chain_next.ptr, c_u64(self.cap), mode,
+                          probe_idx.ptr, build_idx.ptr if build_idx else None,
+                          c_u64(out_cap), cur.ptr)
+            else:
+                shim.call("qk_join_probe_valid", sh, c_u64(n), keys_col.ptr,
+                          bitmap.ptr, self.slot_keys.ptr, self.slot_head.ptr,
+                          self.chain_next.ptr, c_u64(self.cap), mode,
+                          probe_idx.ptr, build_idx.ptr if build_idx else None,
+                          c_u64(out_cap), cur.ptr)
             if self.stream:
                 self.stream.sync()
             total = _read_u64(cur)
             cur.free()
             if total <= out_cap:
+                if owned:
+                    bitmap.free()
                 probe_idx.n = total
                 if build_idx is not None:
                     build_idx.n = total
@@ -438,23 +488,41 @@ class DeviceStringDict:
         doff.free(); dbytes.free(); out.free()
         return codes
 
-    def encode_column(self, col, stream=None):
-        """pyarrow string/large_string column -> np.uint32 codes."""
+    def encode_column(self, col, stream=None, nulls="raise"):
+        """pyarrow string/large_string column -> np.uint32 codes.
+
+        nulls="mask" accepts null strings and returns (codes, mask): mask
+        is a host bool array, True = valid, or None when the column has no
+        nulls. A null row is encoded as whatever bytes its offsets cover
+        (usually none), so its code means nothing and the caller masks
+        it. The default refuses nulls as before."""
         import pyarrow as pa
+        if nulls not in ("raise", "mask"):
+            raise ValueError("nulls must be 'raise' or 'mask', got %r"
+                             % (nulls,))
         if isinstance(col, pa.ChunkedArray):
             col = col.combine_chunks()
         if pa.types.is_dictionary(col.type):
             col = col.dictionary_decode() if hasattr(col, "dictionary_decode") \
                 else col.cast(col.type.value_type)
+        mask = None
         if col.null_count:
-            raise TypeError("null string keys unsupported")
+            if nulls == "raise":
+                raise TypeError("null string keys unsupported")
+            import pyarrow.compute as pc
+            mask = np.ascontiguousarray(
+                pc.is_valid(col).to_numpy(zero_copy_only=False), dtype=bool)
         bufs = col.buffers()
         width = 8 if pa.types.is_large_string(col.type) else 4
         odt = np.int64 if width == 8 else np.int32
         off = np.frombuffer(bufs[1], dtype=odt,
                             count=len(col) + 1 + col.offset)[col.offset:]
-        data = np.frombuffer(bufs[2], dtype=np.uint8)
-        return self.encode(off.astype(np.int64), data, stream)
+        if mask is not None and bufs[2] is None:    # an all-null column
+            data = np.empty(0, dtype=np.uint8)
+        else:
+            data = np.frombuffer(bufs[2], dtype=np.uint8)
+        codes = self.encode(off.astype(np.int64), data, stream)
+        return (codes, mask) if nulls == "mask" else codes
 
     def _ensure(self, n_new, nbytes_new, sh):
         need_codes = self.n_codes + n_new
@@ -540,19 +608,31 @@ class DeviceKeyDict:
     and copies the store, codes never change). What DeviceStringDict is
     for one string column, for the arbitrary groupby_keys / subset lists
     of SQLAggExecutor and DistinctExecutor (sql_executors.py:556-599,
-    :517-554). No key value is reserved; growth is internal."""
+    :517-554). No key value is reserved; growth is internal.
+
+    nullable=True admits NULL keys (DESIGN.md §3a'''): rows are keyed on
+    the K canonical words (0 under a null) plus W = ceil(K / 64) null
+    words, so NULLs of one column equal each other, every null pattern is
+    its own key, and what the caller's column holds under a null does not
+    matter. W is always there, so batches with and without nulls share
+    codes. encode() then takes one validity per key; keys_valid_host()
+    gives the nulls back."""
 
     MAX_CODES = 2 ** 31 - 1
 
-    def __init__(self, nkeys, expected=1024, stream=None):
+    def __init__(self, nkeys, expected=1024, stream=None, nullable=False):
         if int(nkeys) < 1:
             raise ValueError("DeviceKeyDict: nkeys must be >= 1")
         self.nkeys = int(nkeys)
+        self.nullable = bool(nullable)
+        # words per row in slots and store: the keys, then the null words
+        self.nwords = self.nkeys + ((self.nkeys + 63) // 64
+                                    if self.nullable else 0)
         self.stream = stream
         self.cap = _pow2_at_least(max(2, 2 * int(expected)))
         self.slots = self._new_slots(self.cap)
         self.code_cap = max(1, int(expected))
-        self.store = DevColumn(np.int64, self.nkeys * self.code_cap)
+        self.store = DevColumn(np.int64, self.nwords * self.code_cap)
         self._ctr = DevBuffer(8)            # [counter u32, error u32]
         shim.call("qk_dmemset", self._ctr.ptr, 0, c_u64(8))
         self.n_codes = 0
@@ -589,10 +669,10 @@ class DeviceKeyDict:
                 "2**31 - 1 groups" % (self.n_codes, n))
         if need > self.code_cap:
             new_cc = _pow2_at_least(2 * need)
-            new = DevColumn(np.int64, self.nkeys * new_cc)
+            new = DevColumn(np.int64, self.nwords * new_cc)
             shim.call("qk_stream_sync", sh)
             if self.n_codes:
-                for k in range(self.nkeys):
+                for k in range(self.nwords):
                     shim.call(
                         "qk_d2d", shim.c_vp(new.ptr.value + k * new_cc * 8),
                         shim.c_vp(self.store.ptr.value
@@ -608,16 +688,66 @@ class DeviceKeyDict:
             self.cap = _pow2_at_least(2 * need)
             self.slots = self._new_slots(self.cap)
             shim.call("qk_keydict_rehash", sh, c_u32(self.n_codes),
-                      self.nkeys, self.store.ptr, c_u64(self.code_cap),
+                      self.nwords, self.store.ptr, c_u64(self.code_cap),
                       self.slots.ptr, c_u64(self.cap), self._err_ptr)
             self._sync_state(sh, "rehash")
 
-    def encode(self, key_cols, n=None):
+    def _null_words(self, key_cols, valid, n, sh):
+        """The prepare pass of a nullable dictionary (qk_key_null_words):
+        -> (the K + W word columns to encode, temporaries to free once the
+        encode has run)."""
+        if valid is None:
+            valid = [None] * self.nkeys
+        if len(valid) != self.nkeys:
+            raise ValueError("DeviceKeyDict.encode: %d validity entries, "
+                             "expected %d" % (len(valid), self.nkeys))
+        tmp, bitmaps, canon = [], [], []
+
+        def ptr_array(items):
+            ptrs = np.array([0 if x is None else
+                             getattr(x.ptr, "value", x.ptr) or 0
+                             for x in items], dtype=np.uint64)
+            buf = DevBuffer(ptrs.nbytes)
+            tmp.append(buf)
+            shim.call("qk_h2d", buf.ptr, ptrs.ctypes.data_as(c_vp),
+                      c_u64(ptrs.nbytes))
+            return buf.ptr
+        try:
+            for c, v in zip(key_cols, valid):
+                bm, owned = _key_bitmap(c, v, n)
+                if owned:
+                    tmp.append(bm)
+                bitmaps.append(bm)
+                canon.append(None if bm is None else DevColumn(np.int64, n))
+                if bm is not None:
+                    tmp.append(canon[-1])
+            nullw = [DevColumn(np.int64, n)
+                     for _ in range(self.nwords - self.nkeys)]
+            tmp.extend(nullw)
+            shim.call("qk_key_null_words", sh, c_u64(n), self.nkeys,
+                      ptr_array(key_cols), ptr_array(bitmaps),
+                      ptr_array(canon), ptr_array(nullw))
+        except Exception:
+            for t in tmp:
+                t.free()
+            raise
+        words = [c if k is None else k for c, k in zip(key_cols, canon)]
+        return words + nullw, tmp
+
+    def encode(self, key_cols, n=None, valid=None):
         """key_cols: K int64 DevColumns (one 64-bit word per row and key).
-        Returns a DevColumn of u32 codes, n rows; caller frees."""
+        Returns a DevColumn of u32 codes, n rows; caller frees.
+
+        valid (nullable dictionaries only): one entry per key, a device
+        bitmap in the NullableColumn.valid layout, a host bool mask (True
+        = valid) or None for a key without nulls; a NullableColumn among
+        key_cols supplies its own bitmap."""
         if self._broken:
             raise RuntimeError("DeviceKeyDict: unusable after a device "
                                "error")
+        if valid is not None and not self.nullable:
+            raise TypeError("DeviceKeyDict.encode: valid= needs a "
+                            "dictionary made with nullable=True")
         if len(key_cols) != self.nkeys:
             raise ValueError("DeviceKeyDict.encode: %d key columns, "
                              "expected %d" % (len(key_cols), self.nkeys))
@@ -637,9 +767,12 @@ class DeviceKeyDict:
             return out
         sh = self.stream.handle if self.stream else None
         self._ensure(n, sh)
+        tmp = []
+        if self.nullable:
+            key_cols, tmp = self._null_words(key_cols, valid, n, sh)
         dptrs = _dev_ptr_array(key_cols)
         row_slot = DevColumn(np.uint64, n)
-        shim.call("qk_keydict_encode", sh, c_u64(n), self.nkeys, dptrs.ptr,
+        shim.call("qk_keydict_encode", sh, c_u64(n), self.nwords, dptrs.ptr,
                   self.slots.ptr, c_u64(self.cap), self.store.ptr,
                   c_u64(self.code_cap), self._ctr.ptr, row_slot.ptr,
                   out.ptr, self._err_ptr)
@@ -648,10 +781,13 @@ class DeviceKeyDict:
         finally:
             dptrs.free()
             row_slot.free()
+            for t in tmp:
+                t.free()
         return out
 
     def keys_host(self):
-        """-> list of K np.int64 arrays of n_codes words, index == code."""
+        """-> list of K np.int64 arrays of n_codes words, index == code (in
+        a nullable dictionary 0 wherever keys_valid_host() says NULL)."""
         outs = []
         for k in range(self.nkeys):
             a = np.empty(self.n_codes, dtype=np.int64)
@@ -659,6 +795,38 @@ class DeviceKeyDict:
                 shim._bounce.d2h(a, shim.c_vp(
                     self.store.ptr.value + k * self.code_cap * 8))
             outs.append(a)
+        return outs
+
+    def keys_valid_host(self):
+        """-> list of K bool arrays of n_codes entries, index == code,
+        False where that key of the code is NULL (qk_nullword_to_valid
+        over the null-word store columns)."""
+        if not self.nullable:
+            raise TypeError("DeviceKeyDict.keys_valid_host: the dictionary "
+                            "was not made with nullable=True")
+        g = self.n_codes
+        sh = self.stream.handle if self.stream else None
+        nb = valid_nbytes(g)
+        bitmap = DevBuffer(nb)
+        raw = np.empty(nb, dtype=np.uint8)
+        outs = []
+        for k in range(self.nkeys):
+            cnt = _count_buf()
+            shim.call("qk_nullword_to_valid", sh, c_u64(g), shim.c_vp(
+                self.store.ptr.value
+                + (self.nkeys + k // 64) * self.code_cap * 8), k % 64,
+                bitmap.ptr, cnt.ptr)
+            shim.call("qk_stream_sync", sh)
+            shim.call("qk_d2h", raw.ctypes.data_as(c_vp), bitmap.ptr,
+                      c_u64(nb))
+            nulls = _read_u64(cnt)
+            cnt.free()
+            m = np.unpackbits(raw, bitorder="little")[:g].astype(bool)
+            if g - int(m.sum()) != nulls:
+                raise RuntimeError("DeviceKeyDict.keys_valid_host: bitmap "
+                                   "and null count of key %d disagree" % k)
+            outs.append(m)
+        bitmap.free()
         return outs
 
     def free(self):
@@ -673,17 +841,20 @@ class GroupByKeys:
     record of each row's code (SQLAggExecutor's DuckDB group-by over an
     arbitrary groupby_keys list, sql_executors.py:556-599). Because codes
     are dense the accumulate needs no second hash walk and extract() no
-    compaction. Growth is internal; the group limit is 2**31 - 1."""
+    compaction. Growth is internal; the group limit is 2**31 - 1.
+    nullable_keys=True makes NULL a group, one per null pattern across the
+    keys (DeviceKeyDict(nullable=True)); extract_valid() says where."""
 
     AGG_INIT = GroupByI64.AGG_INIT
 
     def __init__(self, nkeys, nvals, agg_ops=None, expected_groups=1024,
-                 stream=None):
+                 stream=None, nullable_keys=False):
         self.nvals = int(nvals)
         self.agg_ops = list(agg_ops) if agg_ops else [0] * self.nvals
         assert len(self.agg_ops) == self.nvals
         self.stream = stream
-        self.dict = DeviceKeyDict(nkeys, expected_groups, stream)
+        self.dict = DeviceKeyDict(nkeys, expected_groups, stream,
+                                  nullable=nullable_keys)
         self.rstride = _pow2_at_least(max(1, self.nvals))
         self._inits_dev = DevColumn.from_numpy(
             np.asarray([self.AGG_INIT[op] for op in self.agg_ops] or [0.0],
@@ -723,7 +894,9 @@ class GroupByKeys:
         self.acc = new
         self.acc_cap = new_cap
 
-    def update(self, key_cols, val_cols, n=None):
+    def update(self, key_cols, val_cols, n=None, key_valid=None):
+        """key_valid: one validity entry per key, as DeviceKeyDict.encode's
+        `valid` (nullable_keys=True only)."""
         assert len(val_cols) == self.nvals
         n = min(c.n for c in key_cols) if n is None else int(n)
         if not n:
@@ -732,7 +905,10 @@ class GroupByKeys:
             if v.dtype != np.dtype(np.float64) or v.n < n:
                 raise TypeError("GroupByKeys.update: value columns are "
                                 "float64 with at least n rows")
-        codes = self.dict.encode(key_cols, n)
+        if key_valid is None:
+            codes = self.dict.encode(key_cols, n)
+        else:
+            codes = self.dict.encode(key_cols, n, valid=key_valid)
         try:
             if not self.nvals:
                 return
@@ -769,6 +945,11 @@ class GroupByKeys:
         sums = np.ascontiguousarray(
             recs.reshape(g, self.rstride)[:, :self.nvals].T)
         return keys, sums
+
+    def extract_valid(self):
+        """-> list of K bool arrays [G], False where that key of group g is
+        NULL; row g belongs to code g, as in extract()."""
+        return self.dict.keys_valid_host()
 
     def free(self):
         self.dict.free()
@@ -868,8 +1049,10 @@ class NullableColumn:
     data) + `valid` (DevBuffer, Arrow validity layout: bit i in byte
     i >> 3, LSB first, 1 = valid; valid_nbytes(n) long, every bit at an
     index >= n is 0). ptr/n/dtype delegate to `values`, so code that only
-    wants the values keeps working. Null join keys, null group keys and
-    null strings are not supported (DESIGN.md §Nullable columns)."""
+    wants the values keeps working. As a key column it supplies its bitmap
+    to JoinTable.build / probe and to a DeviceKeyDict / GroupByKeys made
+    nullable (DESIGN.md §3a'''); those paths never read the value under a
+    null. Null strings outside key columns are not supported."""
 
     def __init__(self, values, valid, n, null_count):
         self.values = values

@@ -149,6 +149,13 @@ _SIGS = {
                           c_vp, c_u64, c_vp, c_vp, c_vp, c_vp],
     "qk_keydict_rehash": [c_vp, c_u32, ctypes.c_int, c_vp, c_u64, c_vp,
                           c_u64, c_vp],
+    "qk_key_null_words": [c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_vp,
+                          c_vp],
+    "qk_nullword_to_valid": [c_vp, c_u64, c_vp, ctypes.c_int, c_vp, c_vp],
+    "qk_join_build_valid": [c_vp, c_u64, c_vp, c_vp, c_u32, c_vp, c_vp,
+                            c_vp, c_u64],
+    "qk_join_probe_valid": [c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                            c_u64, ctypes.c_int, c_vp, c_vp, c_u64, c_vp],
     "qk_groupby_dense_init": [c_vp, c_vp, c_u64, c_u64, ctypes.c_int,
                               ctypes.c_int, c_vp],
     "qk_groupby_dense_acc": [c_vp, c_u64, c_vp, c_u32, c_vp, c_vp,
