@@ -603,6 +603,14 @@ int qk_str_dict_rehash(void *stream, uint32_t ncodes,
                        const uint64_t *code_off, const uint32_t *code_len,
                        const uint8_t *arena, uint64_t *slot_hash,
                        int32_t *slot_code, uint64_t capacity);
+/* Per-row string hash for hash partitioning: out[i] = the dictionary's
+ * 64-bit byte hash of row i (length-seeded splitmix64 fold over 8-byte
+ * little-endian words, zero-padded tail, 0 remapped to 1) shifted right by
+ * one, so it is a non-negative i64 for qk_partition_hist/_scatter. A pure
+ * function of the row's bytes: equal strings get equal values in every
+ * call, process and rank. offsets: i64[n + 1] into bytes. */
+int qk_str_hash_i64(void *stream, uint64_t n, const int64_t *offsets,
+                    const uint8_t *bytes, int64_t *out);
 /* ---- device key dictionary (K full-width key columns) ----------------- *
  * SQLAggExecutor groups by an arbitrary groupby_keys list inside DuckDB
  * (sql_executors.py:556-599) and DistinctExecutor calls

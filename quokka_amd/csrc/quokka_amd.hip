@@ -3083,6 +3083,30 @@ extern "C" int qk_str_dict_rehash(void *stream, uint32_t ncodes,
   return 0;
 }
 
+// String hash partitioning: a row's channel has to be a pure function of
+// its bytes (the same in every call, process and rank), which dictionary
+// codes are not. One row per lane, the dictionary's own hash; the top 63
+// bits as a non-negative i64 feed the integer partition kernels unchanged.
+__global__ void __launch_bounds__(BLOCK) k_str_hash_i64(
+    uint64_t n, const int64_t *__restrict__ offsets,
+    const uint8_t *__restrict__ bytes, int64_t *__restrict__ out) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    int64_t o0 = offsets[i], o1 = offsets[i + 1];
+    out[i] = (int64_t)(qk_str_hash(bytes + o0, (uint32_t)(o1 - o0)) >> 1);
+  }
+}
+extern "C" int qk_str_hash_i64(void *stream, uint64_t n,
+                               const int64_t *offsets, const uint8_t *bytes,
+                               int64_t *out) {
+  if (!n) return 0;
+  hipLaunchKernelGGL(k_str_hash_i64, dim3(qk_grid(n)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, n, offsets, bytes, out);
+  QK_TRY("qk_str_hash_i64", hipGetLastError());
+  return 0;
+}
+
 // ---- device key dictionary: K-word keys -> dense u32 codes -------------
 // SQLAggExecutor groups by an arbitrary groupby_keys list and
 // DistinctExecutor calls unique(subset=keys) (sql_executors.py:556-599,

@@ -50,6 +50,30 @@ def _is_stringish(col):
     return pa.types.is_string(t) or pa.types.is_large_string(t)
 
 
+class _ArrowStrings:
+    """A string key column of gpu_partition_fn kept as its Arrow array
+    (chunks combined, a dictionary decoded) next to the numpy host
+    columns: dtype object like the raw string columns, rows selected
+    with take. The key is hashed on the device from the Arrow offsets
+    and bytes, so no Python string per row is ever made."""
+    dtype = np.dtype(object)
+
+    def __init__(self, col):
+        import pyarrow as pa
+        if isinstance(col, pa.ChunkedArray):
+            col = col.combine_chunks()
+        if pa.types.is_dictionary(col.type):
+            col = col.dictionary_decode() if hasattr(col, "dictionary_decode") \
+                else col.cast(col.type.value_type)
+        self.arr = col
+
+    def __len__(self):
+        return len(self.arr)
+
+    def __getitem__(self, sel):
+        return _ArrowStrings(self.arr.take(sel))
+
+
 def _concat_col(parts):
     import pyarrow as pa
     chunks = []
@@ -1314,7 +1338,18 @@ class GPUTopKExecutor(Executor):
                              reversed(self.descending)):
             v = np.asarray(self.state.column(key).to_numpy(
                 zero_copy_only=False))
-            cols.append(-v if desc else v)
+            if desc:
+                # descending = ascending on the reversed rank of the
+                # distinct values: no arithmetic on the key itself, so
+                # strings, unsigned and INT64_MIN keys order like any
+                # other. NaN (a null) stays last, as it is ascending.
+                _, inv = np.unique(v, return_inverse=True)
+                inv = inv.reshape(-1)
+                rank = inv.max() - inv
+                if v.dtype.kind == "f":
+                    rank[np.isnan(v)] = len(v)
+                v = rank
+            cols.append(v)
         order = np.lexsort(cols)[: self.k]
         return self.state.take(order)
 
@@ -1377,6 +1412,8 @@ def gpu_partition_fn(data, source_channel, num_target_channels, key=None,
         except TypeError:
             col = data.column(c)
             if _is_stringish(col):       # general strings: host object
+                if c == key:             # hashed from its Arrow buffers
+                    return _ArrowStrings(col)
                 return np.asarray(col.to_pylist(), dtype=object)
             raise
 
@@ -1472,26 +1509,26 @@ def gpu_partition_fn(data, source_channel, num_target_channels, key=None,
             c.free()
 
     keys = host_cols[key]
-    if keys.dtype == object:
-        # string partition keys: device string dictionary -> dense codes
-        # (the reference hashes strings inside polars,
-        # quokka_runtime.py:224 — an un-vendored implementation detail;
-        # the preserved contract is equal keys -> same channel, which
-        # code % N gives. Range partitioning needs an ordered key.)
+    if isinstance(keys, _ArrowStrings):
+        # string partition keys: a row's channel is (byte hash >> 1) % N,
+        # a pure function of the key's bytes, so a key
+        # meets its equals on one channel whichever batch, producer or
+        # rank sent it. (The reference hashes strings inside polars,
+        # quokka_runtime.py:224; its bucket ids are an implementation
+        # detail, the contract is equal keys -> same channel. Range
+        # partitioning needs an ordered key.)
         if partitioner != "hash":
             raise TypeError("string keys support hash partitioning only")
-        import pyarrow as _pa
-        sd = ops.DeviceStringDict(expected=max(1024, len(keys)))
-        keys = sd.encode_column(
-            _pa.chunked_array([_pa.array(keys)])).astype(np.int64)
-        sd.free()
-    if keys.dtype != np.int64:
-        if keys.dtype.kind in "iu":
-            keys = keys.astype(np.int64)
-        else:
-            raise TypeError("gpu_partition_fn: integer or string keys, "
-                            "got %s" % keys.dtype)
-    kcol = shim.DevColumn.from_numpy(keys)
+        kcol = ops.str_hash_i64(keys.arr)
+        host_cols[key] = keys.arr
+    else:
+        if keys.dtype != np.int64:
+            if keys.dtype.kind in "iu":
+                keys = keys.astype(np.int64)
+            else:
+                raise TypeError("gpu_partition_fn: integer or string keys, "
+                                "got %s" % keys.dtype)
+        kcol = shim.DevColumn.from_numpy(keys)
     if partitioner == "range":
         assert total_range, "range partitioner needs total_range"
         from .shim import DevColumn, c_u64, c_i64, c_u32
@@ -1510,7 +1547,8 @@ def gpu_partition_fn(data, source_channel, num_target_channels, key=None,
         if hi == lo:
             continue
         rows = sel[lo:hi]
-        out[p] = pa.table({c: host_cols[c][rows] for c in names})
+        # ndarray.take for the host columns, Array.take for a string key
+        out[p] = pa.table({c: host_cols[c].take(rows) for c in names})
     kcol.free()
     idx.free()
     return out

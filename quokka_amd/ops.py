@@ -412,6 +412,68 @@ class GroupByI64:
             self._ops_dev.free()
 
 
+def _arrow_string_buffers(col, who):
+    """pyarrow string / large_string Array -> (offsets np.int64[n + 1]
+    into data, data np.uint8), read with the offset width of the column's
+    own type. Any other type is refused by name: binary and large_binary
+    share the layout but are not strings, and anything else would be read
+    with the wrong width. Arrow may leave out the data buffer (and, for an
+    empty array, the offsets) when no row has bytes."""
+    import pyarrow as pa
+    large = pa.types.is_large_string(col.type)
+    if not (large or pa.types.is_string(col.type)):
+        raise TypeError("%s: not a string column (%s)" % (who, col.type))
+    n = len(col)
+    bufs = col.buffers()
+    if n == 0 or bufs[1] is None:
+        off = np.zeros(n + 1, dtype=np.int64)
+    else:
+        off = np.frombuffer(bufs[1], dtype=np.int64 if large else np.int32,
+                            count=col.offset + n + 1)[col.offset:]
+        off = off.astype(np.int64)
+    if bufs[2] is None or bufs[2].size == 0:
+        data = np.empty(0, dtype=np.uint8)
+    else:
+        data = np.frombuffer(bufs[2], dtype=np.uint8)
+    return off, data
+
+
+def str_hash_i64(col, stream=None):
+    """pyarrow string / large_string / dictionary-of-string Array or
+    ChunkedArray without nulls -> DevColumn i64 of n rows: the string
+    dictionary's byte hash of each row, shifted right by one
+    (qk_str_hash_i64). A pure function of the row's bytes, so
+    partition_i64 over it places a string on the same channel in every
+    call, process and rank."""
+    import pyarrow as pa
+    if isinstance(col, pa.ChunkedArray):
+        col = col.combine_chunks()
+    if pa.types.is_dictionary(col.type):
+        col = col.dictionary_decode() if hasattr(col, "dictionary_decode") \
+            else col.cast(col.type.value_type)
+    off, data = _arrow_string_buffers(col, "str_hash_i64")
+    if col.null_count:
+        raise TypeError("null string keys unsupported")
+    n = len(col)
+    out = DevColumn(np.int64, n)
+    if n == 0:
+        return out
+    lo, hi = int(off[0]), int(off[-1])
+    doff = DevColumn.from_numpy(off - lo if lo else off)
+    dbytes = DevBuffer(max(1, hi - lo))
+    if hi > lo:
+        shim._bounce.h2d(dbytes.ptr, data[lo:hi])
+    sh = stream.handle if stream else None
+    shim.call("qk_str_hash_i64", sh, c_u64(n), doff.ptr, dbytes.ptr, out.ptr)
+    if stream:
+        stream.sync()
+    else:
+        shim.call("qk_stream_sync", None)
+    doff.free()
+    dbytes.free()
+    return out
+
+
 class DeviceStringDict:
     """Device-resident accumulating string dictionary: arbitrary-width,
     unbounded-cardinality string keys -> dense u32 codes, consistent
@@ -439,7 +501,8 @@ class DeviceStringDict:
         shim.call("qk_dmemset", self._ctr.ptr, 0, c_u64(16))
         self.n_codes = 0
         self.arena_used = 0
-        self._values = []                   # host cache, len == decoded so far
+        self._values = []                   # host cache of bytes, by code
+        self._strs = []                     # their decoded view, by code
 
     def _alloc_table(self, cap):
         self.slot_hash = DevColumn(np.uint64, cap)
@@ -505,6 +568,8 @@ class DeviceStringDict:
         if pa.types.is_dictionary(col.type):
             col = col.dictionary_decode() if hasattr(col, "dictionary_decode") \
                 else col.cast(col.type.value_type)
+        off, data = _arrow_string_buffers(col, "DeviceStringDict."
+                                          "encode_column")
         mask = None
         if col.null_count:
             if nulls == "raise":
@@ -512,16 +577,7 @@ class DeviceStringDict:
             import pyarrow.compute as pc
             mask = np.ascontiguousarray(
                 pc.is_valid(col).to_numpy(zero_copy_only=False), dtype=bool)
-        bufs = col.buffers()
-        width = 8 if pa.types.is_large_string(col.type) else 4
-        odt = np.int64 if width == 8 else np.int32
-        off = np.frombuffer(bufs[1], dtype=odt,
-                            count=len(col) + 1 + col.offset)[col.offset:]
-        if mask is not None and bufs[2] is None:    # an all-null column
-            data = np.empty(0, dtype=np.uint8)
-        else:
-            data = np.frombuffer(bufs[2], dtype=np.uint8)
-        codes = self.encode(off.astype(np.int64), data, stream)
+        codes = self.encode(off, data, stream)
         return (codes, mask) if nulls == "mask" else codes
 
     def _ensure(self, n_new, nbytes_new, sh):
@@ -558,8 +614,10 @@ class DeviceStringDict:
             self.arena_cap = new_ac
 
     @property
-    def values(self):
-        """Decoded strings, index == code (lazily materialized)."""
+    def values_bytes(self):
+        """The stored strings as `bytes`, index == code (lazily
+        materialized). Whatever encode() was given comes back as it is,
+        UTF-8 or not."""
         if len(self._values) < self.n_codes:
             k0 = len(self._values)
             k = self.n_codes - k0
@@ -575,8 +633,17 @@ class DeviceStringDict:
             raw = blob.tobytes()
             for o, ln in zip(offs, lens):
                 s = int(o) - lo
-                self._values.append(raw[s:s + int(ln)].decode())
+                self._values.append(raw[s:s + int(ln)])
         return self._values
+
+    @property
+    def values(self):
+        """Decoded strings, index == code: the UTF-8 view of
+        values_bytes."""
+        raw = self.values_bytes
+        for b in raw[len(self._strs):]:
+            self._strs.append(b.decode())
+        return self._strs
 
     def decode(self, codes):
         vals = np.asarray(self.values, dtype=object)

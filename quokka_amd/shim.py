@@ -145,6 +145,7 @@ _SIGS = {
                            c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "qk_str_dict_rehash": [c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp,
                            c_u64],
+    "qk_str_hash_i64": [c_vp, c_u64, c_vp, c_vp, c_vp],
     "qk_keydict_encode": [c_vp, c_u64, ctypes.c_int, c_vp, c_vp, c_u64,
                           c_vp, c_u64, c_vp, c_vp, c_vp, c_vp],
     "qk_keydict_rehash": [c_vp, c_u32, ctypes.c_int, c_vp, c_u64, c_vp,

@@ -34,7 +34,9 @@ def test_header_declares_expected_surface():
     assert len(syms) >= 30
     for must in ("qk_q1_agg", "qk_q6_agg", "qk_join_build", "qk_join_probe",
                  "qk_groupby_i64_sum", "qk_partition_hist", "qk_filter_i32",
-                 "qk_gen_lineitem", "qk_block_threads", "qk_max_blocks"):
+                 "qk_gen_lineitem", "qk_block_threads", "qk_max_blocks",
+                 "qk_str_dict_encode", "qk_str_dict_rehash",
+                 "qk_str_hash_i64"):
         assert must in syms
 
 
@@ -76,7 +78,8 @@ def test_shim_signatures_match_header_prototypes():
         return {"uint64_t": ct.c_uint64, "uint8_t": ct.c_uint8,
                 "int": ct.c_int}[param.split()[0]]
     for name in ("qk_csv_newlines", "qk_csv_newlines_quoted",
-                 "qk_csv_parse", "qk_pq_rle_pages", "qk_pq_def_pages"):
+                 "qk_csv_parse", "qk_pq_rle_pages", "qk_pq_def_pages",
+                 "qk_str_hash_i64"):
         assert [kind(p) for p in protos[name]] == shim._SIGS[name], name
     # qk_pq_rle_pages ends with the per-page error table
     assert [p.split()[-1].lstrip("*") for p in protos["qk_pq_rle_pages"]] \
@@ -255,3 +258,55 @@ def test_jit_translate_r02_tail_expressions():
     import pytest as _pytest
     with _pytest.raises(Exception):
         jit.translate_arith("a > 1", {"a": np.dtype(np.float64)})
+
+
+def _topk_want(t, keys, desc, k):
+    return t.sort_by([(c, "descending" if d else "ascending")
+                      for c, d in zip(keys, desc)]).slice(0, k)
+
+
+def test_topk_executor_descending_string_key_cpu():
+    """A descending string sort key, alone and as the second of two keys
+    (negating the key is a TypeError on strings): == sort_by + slice."""
+    import numpy as np
+    import pyarrow as pa
+    from quokka_amd import GPUTopKExecutor
+    rng = np.random.default_rng(5)
+    pool = np.array(["", "a", "a\0", "ab", "abc", "b", "é",
+                     "日本", "日本語", "z"], dtype=object)
+    n = 400
+    t = pa.table({"s": pa.array(rng.choice(pool, n)),
+                  "g": rng.integers(0, 5, n),
+                  "id": np.arange(n)})
+    for keys, desc in ((["s", "id"], [True, False]),
+                       (["g", "s", "id"], [False, True, False]),
+                       (["g", "s", "id"], [True, True, True]),
+                       (["s", "id"], [False, True])):
+        ex = GPUTopKExecutor(keys, 37, descending=desc)
+        ex.execute([t.slice(0, 150)], 0, 0)
+        ex.execute([t.slice(150)], 0, 0)
+        out = ex.done(0)
+        assert out.column("id").to_pylist() == \
+            _topk_want(t, keys, desc, 37).column("id").to_pylist(), (keys, desc)
+    ex = GPUTopKExecutor(["s"], 5, descending=[True])
+    ex.execute([t], 0, 0)
+    assert ex.done(0).column("s").to_pylist() == \
+        _topk_want(t, ["s"], [True], 5).column("s").to_pylist()
+
+
+def test_topk_executor_descending_needs_no_arithmetic_cpu():
+    """Descending keys whose negation wraps or is undefined: uint64 above
+    2**63, INT64_MIN and bool order like any other; NaN stays last."""
+    import numpy as np
+    import pyarrow as pa
+    from quokka_amd import GPUTopKExecutor
+    u = np.array([2 ** 63 + 5, 1, 2 ** 64 - 1, 0, 7], dtype=np.uint64)
+    i = np.array([-2 ** 63, 5, -1, 2 ** 63 - 1, 0], dtype=np.int64)
+    b = np.array([True, False, True, False, False])
+    f = np.array([1.5, np.nan, -2.0, 9.0, np.nan])
+    t = pa.table({"u": u, "i": i, "b": b, "f": f, "id": np.arange(5)})
+    for key, want in (("u", [2, 0, 4, 1, 3]), ("i", [3, 1, 4, 2, 0]),
+                      ("b", [0, 2, 1, 3, 4]), ("f", [3, 0, 2, 1, 4])):
+        ex = GPUTopKExecutor([key, "id"], 5, descending=[True, False])
+        ex.execute([t], 0, 0)
+        assert ex.done(0).column("id").to_pylist() == want, key

@@ -272,3 +272,247 @@ def test_sort_executor_string_key(gpu):
     for i in range(1, len(got)):
         if got[i] == got[i - 1]:
             assert gv[i] > gv[i - 1]
+
+
+# ---- string hash partitioning: a pure function of the key's bytes -------
+
+def _check_partition(parts, keys, v, x, nparts):
+    """Every row on the channel the host model names for its key, payload
+    still beside its key, no row lost or made up."""
+    import _str_cases as S
+    n_out = 0
+    rows = []
+    for ch, tbl in parts.items():
+        assert 0 <= ch < nparts and tbl.num_rows > 0
+        n_out += tbl.num_rows
+        ks = tbl.column("k").to_pylist()
+        for k in set(ks):
+            assert S.channel_of(k.encode(), nparts) == ch, k
+        rows.extend(zip(ks, tbl.column("v").to_pylist(),
+                        tbl.column("x").to_pylist()))
+    assert n_out == len(keys)
+    assert sorted(rows) == sorted(zip(keys, v.tolist(), x.tolist()))
+    return {ch for ch in parts}
+
+
+def test_partition_fn_string_keys_stable_across_calls(gpu):
+    """The same 512 keys through three calls (permuted, as subsets, from
+    different source channels, in both offset widths and in chunks): each
+    key sits on the channel tests/_str_cases.channel_of names, in every
+    call. Codes of a per-call dictionary cannot do that."""
+    import _str_cases as S
+    from quokka_amd import gpu_partition_fn
+    N = S.PARTITION_N
+    pool = np.array([k.decode() for k in S.partition_keys()], dtype=object)
+    number = {k: i for i, k in enumerate(pool)}
+    rng = np.random.default_rng(91)
+    calls = [
+        (0, np.concatenate([rng.permutation(pool) for _ in range(3)]),
+         lambda a: pa.array(a)),
+        (1, rng.choice(pool[:200], 700),
+         lambda a: pa.array(a, type=pa.large_string())),
+        (3, rng.choice(pool[150:], 900),
+         lambda a: pa.chunked_array([pa.array(a[:333]), pa.array(a[333:])])),
+    ]
+    for src, keys, make in calls:
+        v = np.array([number[k] for k in keys], dtype=np.int64)
+        x = rng.random(len(keys))
+        t = pa.table({"k": make(keys), "v": v, "x": x})
+        parts = gpu_partition_fn(t, src, N, key="k")
+        used = _check_partition(parts, list(keys), v, x, N)
+        for tbl in parts.values():
+            assert tbl.column("v").to_pylist() == [
+                number[k] for k in tbl.column("k").to_pylist()]
+        if src == 0:
+            assert used == set(range(N))
+
+
+def test_partition_fn_string_keys_colliding_and_edges(gpu):
+    """Strings with one 64-bit hash share a channel and lose no rows; the
+    length and tail edges go where the model says; a predicate in front of
+    a string key keeps key and payload together."""
+    import _str_cases as S
+    from quokka_amd import gpu_partition_fn
+    groups = [S.colliding(24, 4, seed=s) for s in (41, 42, 43)]
+    for g in groups:
+        assert len({S.channel_of(b, 3) for b in g}) == 1
+    pool = np.array([b.decode() for g in groups for b in g] +
+                    [b.decode() for b in S.EDGES], dtype=object)
+    rng = np.random.default_rng(92)
+    keys = rng.choice(pool, 2000)
+    v = np.arange(2000, dtype=np.int64)
+    x = rng.random(2000)
+    t = pa.table({"k": pa.array(keys), "v": v, "x": x})
+    for nparts in (3, 4):
+        _check_partition(gpu_partition_fn(t, 0, nparts, key="k"),
+                         list(keys), v, x, nparts)
+    keep = v >= 700
+    parts = gpu_partition_fn(t, 2, 4, key="k", predicate="v >= 700")
+    _check_partition(parts, list(keys[keep]), v[keep], x[keep], 4)
+
+
+def test_partition_fn_string_key_range_raises(gpu):
+    from quokka_amd import gpu_partition_fn
+    t = pa.table({"k": pa.array(["a", "b", "c"]), "v": [1, 2, 3]})
+    with pytest.raises(TypeError, match="hash partitioning only"):
+        gpu_partition_fn(t, 0, 2, key="k", partitioner="range",
+                         total_range=100)
+
+
+# ---- executors under the adversarial strings of tests/_str_cases.py -----
+
+def _row_multiset(tbl, cols):
+    """Rows of `cols` as a sorted list of tuples, None ordered first."""
+    lists = [tbl.column(c).to_pylist() for c in cols]
+    return sorted(zip(*lists),
+                  key=lambda r: tuple((x is not None, x) if x is not None
+                                      else (False, 0) for x in r))
+
+
+@pytest.fixture
+def table_allocs(monkeypatch):
+    """Slot-table sizes every DeviceStringDict allocates during the test:
+    more than one size means a dictionary grew."""
+    from quokka_amd import ops
+    sizes = []
+    orig = ops.DeviceStringDict._alloc_table
+
+    def counting(self, cap):
+        sizes.append(cap)
+        return orig(self, cap)
+    monkeypatch.setattr(ops.DeviceStringDict, "_alloc_table", counting)
+    return sizes
+
+
+_ACERO_HOW = {"inner": "inner", "left": "left outer", "semi": "left semi",
+              "anti": "left anti"}
+
+
+@pytest.mark.parametrize("variant", ["build_probe", "broadcast"])
+@pytest.mark.parametrize("how", ["inner", "left", "semi", "anti"])
+def test_string_key_join_colliding_keys(gpu, table_allocs, how, variant):
+    """The build side holds one string of each colliding group, the probe
+    side the others (equal hash, no match) next to true matches. Two probe
+    batches; the second brings enough new strings to grow the shared
+    dictionary. Rows == Acero's."""
+    import _str_cases as S
+    from quokka_amd.executors import (GPUBuildProbeJoinExecutor,
+                                      GPUBroadcastJoinExecutor)
+    groups = [[b.decode() for b in S.colliding(16 + 3 * s, 4, seed=50 + s)]
+              for s in range(4)]
+    edges = [b.decode() for b in S.EDGES]
+    bkeys = [g[0] for g in groups] + edges[::2] + \
+        ["b%d" % i for i in range(300)]
+    build = pa.table({"k": pa.array(bkeys),
+                      "pay": np.arange(len(bkeys), dtype=np.float64)})
+    pool = np.array([s for g in groups for s in g] + edges +
+                    ["b%d" % i for i in range(0, 600, 3)], dtype=object)
+    rng = np.random.default_rng(93)
+    k1 = rng.choice(pool, 1500)     # fits the dictionary as built
+    k2 = np.concatenate([rng.choice(pool, 1000),
+                         np.array(["new%d" % i for i in range(3000)],
+                                  dtype=object)])
+    rng.shuffle(k2)
+    if variant == "build_probe":
+        ex = GPUBuildProbeJoinExecutor(left_on="k", right_on="k", how=how)
+        h = len(bkeys) // 2
+        ex.execute([build.slice(0, h)], 1, 0)
+        ex.execute([build.slice(h)], 1, 0)
+    else:
+        ex = GPUBroadcastJoinExecutor(build, on="k", how=how)
+    cols = ["k", "x"] + (["pay"] if how in ("inner", "left") else [])
+    for j, ks in enumerate((k1, k2)):
+        probe = pa.table({"k": pa.array(ks),
+                          "x": np.arange(len(ks), dtype=np.float64) + j})
+        got = ex.execute([probe], 0, 0)
+        want = probe.join(build, keys="k", join_type=_ACERO_HOW[how])
+        assert got.num_rows == want.num_rows
+        assert _row_multiset(got, cols) == _row_multiset(want, cols)
+    assert len(set(table_allocs)) >= 2      # grew under the second batch
+
+
+def _agg_batches():
+    """Three batches over colliding, edge and plain strings; each brings
+    strings the earlier ones did not have, the last enough rows to grow a
+    dictionary sized for 4096 strings."""
+    import _str_cases as S
+    special = [b.decode() for s in (61, 62) for b in S.colliding(24, 4, s)] \
+        + [b.decode() for b in S.EDGES]
+    plain = ["g%d" % i for i in range(3200)]
+    rng = np.random.default_rng(94)
+    out = []
+    for lo, hi, extra in ((0, 1500, 1000), (1500, 3000, 1000),
+                          (3000, 3200, 5500)):
+        ks = np.array(plain[lo:hi] + special +
+                      list(rng.choice(np.array(plain[:hi] + special,
+                                               dtype=object), extra)),
+                      dtype=object)
+        rng.shuffle(ks)
+        out.append(pa.table({"k": pa.array(ks), "v": rng.random(len(ks))}))
+    return out
+
+
+@pytest.mark.parametrize("device_keys", [False, True])
+def test_string_key_groupby_colliding_and_edges(gpu, table_allocs,
+                                                device_keys):
+    from quokka_amd.executors import GPUAggExecutor
+    batches = _agg_batches()
+    ex = GPUAggExecutor(["k"], [("k", "asc")], "sum(v) as s",
+                        device_keys=device_keys)
+    for b in batches:
+        ex.execute([b], 0, 0)
+    out = ex.done(0)
+    assert len(set(table_allocs)) >= 2      # the dictionary grew
+    want = pa.concat_tables(batches).group_by("k").aggregate(
+        [("v", "sum")])
+    wsum = dict(zip(want.column("k").to_pylist(),
+                    want.column("v_sum").to_pylist()))
+    ks = out.column("k").to_pylist()
+    assert len(ks) == len(wsum) and set(ks) == set(wsum)
+    assert ks == sorted(ks, key=lambda s: s.encode())
+    np.testing.assert_allclose(np.asarray(out.column("s")),
+                               np.array([wsum[k] for k in ks]), rtol=1e-9)
+
+
+def test_distinct_executor_colliding_and_edges(gpu, table_allocs):
+    """First occurrences in arrival order, batch by batch, as
+    test_distinct_executor_string_keys defines it."""
+    from quokka_amd.executors import GPUDistinctExecutor
+    ex = GPUDistinctExecutor("k")
+    seen = set()
+    for b in _agg_batches():
+        keys = b.column("k").to_pylist()
+        out = ex.execute([b], 0, 0)
+        new = [k for k in dict.fromkeys(keys) if k not in seen]
+        assert new
+        assert out.column("k").to_pylist() == new
+        first = {}
+        for k, v in zip(keys, b.column("v").to_pylist()):
+            first.setdefault(k, v)
+        assert out.column("v").to_pylist() == [first[k] for k in new]
+        seen.update(keys)
+    assert len(set(table_allocs)) >= 2
+
+
+def test_sort_executor_string_edges(gpu):
+    """Empty string, prefixes, multi-byte UTF-8 and colliding strings:
+    the order is that of the UTF-8 bytes, and the sort is stable."""
+    import _str_cases as S
+    from quokka_amd.executors import GPUSortExecutor
+    pool = np.array([b.decode() for b in S.EDGES] +
+                    [b.decode() for b in S.colliding(24, 4, seed=71)] +
+                    ["ab", "abc", "abcd", "b", "\u00e9z", "z"],
+                    dtype=object)
+    rng = np.random.default_rng(95)
+    keys = rng.choice(pool, 3000)
+    t = pa.table({"k": pa.array(keys), "v": np.arange(3000.0)})
+    ex = GPUSortExecutor("k")
+    ex.execute([t.slice(0, 1700)], 0, 0)
+    ex.execute([t.slice(1700)], 0, 0)
+    out = ex.done(0)
+    got = out.column("k").to_pylist()
+    assert got == sorted(keys, key=lambda s: s.encode())
+    gv = np.asarray(out.column("v"))
+    same = np.array([got[i] == got[i - 1] for i in range(1, len(got))])
+    assert (np.diff(gv)[same] > 0).all()
+    assert sorted(gv.tolist()) == list(range(3000))
