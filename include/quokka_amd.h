@@ -706,6 +706,28 @@ int qk_groupby_dense_acc(void *stream, uint64_t n, const uint32_t *codes,
                          const void *vals_dev /* dev double*[nvals] */,
                          const int32_t *agg_ops_dev, int nvals, int rstride,
                          double *acc, uint32_t *err_dev);
+/* qk_groupby_dense_acc over value columns with SQL NULLs: SUM / MIN / MAX
+ * skip them, and an aggregate that met no value is NULL (DuckDB's GROUP BY,
+ * pyarrow Acero with min_count = 1).
+ * valid_ptrs_dev: device array of nvals bitmap pointers (layout under
+ *   "nullable columns" above; at least ceil(n / 64) whole words; the bits of
+ *   the last word at row indices >= n may hold anything); 0 = column c has
+ *   no nulls, and then nothing of a bitmap is read for it. Where a row's bit
+ *   is 0 the value word under it is not read and nothing of that row
+ *   reaches column c's accumulator.
+ * seen: one u64 per code, beside the records and zeroed by the caller for
+ *   new codes; bit c of seen[code] is set once column c of that group has
+ *   received a value, so nvals <= 64. Records keep the layout and the
+ *   identities of qk_groupby_dense_init: an aggregate whose seen bit is 0
+ *   still holds its identity. A code >= ncodes writes neither. */
+int qk_groupby_dense_acc_valid(void *stream, uint64_t n,
+                               const uint32_t *codes, uint32_t ncodes,
+                               const void *vals_dev /* dev double*[nvals] */,
+                               const void *valid_ptrs_dev
+                               /* dev uint64_t*[nvals] */,
+                               const int32_t *agg_ops_dev, int nvals,
+                               int rstride, double *acc, uint64_t *seen,
+                               uint32_t *err_dev);
 /* ---- LIKE over free-text string columns ------------------------------- *
  * The reference hands `col LIKE 'pat'` / NOT LIKE / = / <> on varchar
  * columns to DuckDB or polars inside filter_sql (core.py:157-163; the

@@ -3472,6 +3472,75 @@ extern "C" int qk_groupby_dense_acc(void *stream, uint64_t n,
   return 0;
 }
 
+// The same accumulate over value columns with SQL NULLs (DuckDB's SUM / MIN
+// / MAX skip them, and an aggregate that met no value is NULL,
+// sql_executors.py:556-599). valid[c] is column c's validity bitmap or 0
+// for a column without nulls, tested before anything of it is read. As in
+// k_key_null_words a wave covers 64 consecutive, 64-aligned rows, so a
+// column's validity word is one load of the same address for the whole
+// wave and each lane tests its own bit; only lanes with i < n run, so the
+// bits of the last word past n reach nothing, and the value under a 0 bit
+// is never loaded. seen[code] collects one bit per column that has
+// received a value. The plain read in front of the atomicOr can only be
+// stale towards fewer bits: it costs a redundant atomic, never a lost one,
+// and once a group's bits stand its rows pay one mostly-cached load.
+__global__ void __launch_bounds__(BLOCK) k_groupby_dense_acc_valid(
+    uint64_t n, const uint32_t *__restrict__ codes, uint32_t ncodes,
+    const double *const *__restrict__ vals,
+    const uint64_t *const *__restrict__ valid,
+    const int32_t *__restrict__ agg_ops, int nvals, int rstride, double *acc,
+    uint64_t *seen, uint32_t *err) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  uint32_t lane = threadIdx.x & (WAVE - 1);
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    uint32_t code = codes[i];
+    if (code >= ncodes) {  // never written past the records the host sized
+      atomicOr(err, 4u);
+      continue;
+    }
+    double *rec = acc + (uint64_t)code * (uint64_t)rstride;
+    uint64_t m = 0;
+    for (int c = 0; c < nvals; c++) {
+      const uint64_t *vp = valid[c];
+      if (vp && !((vp[i >> 6] >> lane) & 1)) continue;
+      double v = vals[c][i];
+      int op = agg_ops ? agg_ops[c] : 0;
+      if (op == 1)
+        atomic_min_f64(&rec[c], v);
+      else if (op == 2)
+        atomic_max_f64(&rec[c], v);
+      else
+        atomicAdd(&rec[c], v);
+      m |= 1ULL << c;
+    }
+    if (m && (seen[code] & m) != m)
+      atomicOr((unsigned long long *)&seen[code], (unsigned long long)m);
+  }
+}
+extern "C" int qk_groupby_dense_acc_valid(void *stream, uint64_t n,
+                                          const uint32_t *codes,
+                                          uint32_t ncodes,
+                                          const void *vals_dev,
+                                          const void *valid_ptrs_dev,
+                                          const int32_t *agg_ops_dev,
+                                          int nvals, int rstride, double *acc,
+                                          uint64_t *seen, uint32_t *err_dev) {
+  if (!n || !nvals) return 0;
+  if (nvals < 0 || nvals > 64 || rstride < nvals ||
+      !qk_pow2((uint64_t)rstride))
+    return qk_fail("qk_groupby_dense_acc_valid.rstride", hipErrorInvalidValue);
+  if (!codes || !vals_dev || !valid_ptrs_dev || !acc || !seen || !err_dev)
+    return qk_fail("qk_groupby_dense_acc_valid.args", hipErrorInvalidValue);
+  hipLaunchKernelGGL(k_groupby_dense_acc_valid, dim3(qk_grid(n)), dim3(BLOCK),
+                     0, (hipStream_t)stream, n, codes, ncodes,
+                     (const double *const *)vals_dev,
+                     (const uint64_t *const *)valid_ptrs_dev, agg_ops_dev,
+                     nvals, rstride, acc, seen, err_dev);
+  QK_TRY("qk_groupby_dense_acc_valid", hipGetLastError());
+  return 0;
+}
+
 // ---- LIKE over free-text string columns --------------------------------
 // filter_sql("o_comment not like '%special%requests%'") and its kin
 // (apps/tpc-h/tpch.py:137,316,380,413,416,481) run inside DuckDB/polars in

@@ -622,25 +622,50 @@ class GPUAggExecutor(Executor):
     null pattern across the keys, as DuckDB's GROUP BY does: done() returns
     the key columns in their Arrow types with the nulls in place, and an
     order-by over such a key puts its NULLs last in both directions
-    (DESIGN.md §3a'''). Nulls in the aggregated value columns stay
-    unsupported."""
+    (DESIGN.md §3a''').
+
+    null_values=True admits NULLs in the aggregated value columns, with
+    DuckDB's rules (DESIGN.md §3a''''): SUM / MIN / MAX skip them, an
+    aggregate whose inputs were all NULL is NULL, and an output expression
+    is NULL for a group when any aggregate it references is. Such an alias
+    comes back as an Arrow float64 column with the nulls in place, and an
+    order-by over it puts them last in both directions; an alias without a
+    NULL comes back as it does by default. With group keys it needs
+    device_keys=True (the hash-table path has no place to remember that a
+    group met no value); a grand aggregate (groupby_keys == []) takes it as
+    it is. It combines freely with null_keys=True, takes at most 64
+    accumulators, and lets one column stand under several functions
+    (min(b) beside max(b), one accumulator each), which the default
+    refuses. By default a NULL in a value column arrives as NaN
+    (an integer column with nulls turns float on the way) and is
+    accumulated like any other value: one NULL makes its group's SUM NaN,
+    and a MIN / MAX keeps whatever the comparison with NaN leaves."""
 
     def __init__(self, groupby_keys, orderby_keys, sql_statement,
-                 device_keys=False, null_keys=False):
+                 device_keys=False, null_keys=False, null_values=False):
         if not isinstance(groupby_keys, list):
             raise TypeError("groupby_keys must be a list (may be empty "
                             "for a grand aggregate)")
         if null_keys and not device_keys:
             raise ValueError("null_keys=True needs device_keys=True: the "
                              "composite key encoding has no place for NULL")
+        if null_values and groupby_keys and not device_keys:
+            raise ValueError("null_values=True with group keys needs "
+                             "device_keys=True: the hash-table path keeps "
+                             "no record of which aggregates met a value")
         self.groupby_keys = groupby_keys
         self.orderby_keys = orderby_keys or []
         self.sql_statement = sql_statement
         self.device_keys = bool(device_keys)
         self.null_keys = bool(null_keys)
+        self.null_values = bool(null_values)
         self.sum_cols = []          # partial columns referenced by aggs
         self.agg_ops = []           # per column: 0 SUM / 1 MIN / 2 MAX
         self.exprs = []             # (alias, python expr over s['col'])
+        # name of each accumulator in `s`: its column, or 'fn(col)' for a
+        # further function over a column that has one (null_values only)
+        self.agg_names = []
+        self.expr_cols = []         # per expr: the accumulators it reads
         for part in self._split_top(sql_statement):
             alias = None
             m = re.search(r"\s+as\s+([A-Za-z_][A-Za-z0-9_]*)\s*$", part,
@@ -671,14 +696,37 @@ class GPUAggExecutor(Executor):
                 if c not in self.sum_cols:
                     self.sum_cols.append(c)
                     self.agg_ops.append(_AGG_OP[fn.lower()])
-                elif self.agg_ops[self.sum_cols.index(c)] != _AGG_OP[fn.lower()]:
-                    raise ValueError("column %r used with two different "
-                                     "aggregate functions" % c)
-            expr = _AGG_RE.sub(lambda m: "s[%r]" % m.group(2), part)
+                    self.agg_names.append(c)
+                elif self._agg_name(fn, c) is None:
+                    # min(b) beside max(b): DuckDB takes it, and the left
+                    # join's NULL payloads ask for both at once; each
+                    # function is one more accumulator over the column
+                    if not self.null_values:
+                        raise ValueError("column %r used with two different "
+                                         "aggregate functions" % c)
+                    self.sum_cols.append(c)
+                    self.agg_ops.append(_AGG_OP[fn.lower()])
+                    self.agg_names.append("%s(%s)" % (fn.lower(), c))
+            expr = _AGG_RE.sub(
+                lambda m: "s[%r]" % self._agg_name(m.group(1), m.group(2)),
+                part)
             self.exprs.append((alias or part.strip(), expr))
+            self.expr_cols.append(sorted({self._agg_name(fn, c)
+                                          for fn, c in hits}))
+        if self.null_values and len(self.sum_cols) > 64:
+            raise ValueError("null_values=True takes at most 64 aggregated "
+                             "columns, got %d" % len(self.sum_cols))
         self._gb = None
         self._key_state = None
         self._key_words = None      # _KeyWords of the device_keys path
+
+    def _agg_name(self, fn, col):
+        """Name in `s` of the accumulator of fn(col), None without one."""
+        op = _AGG_OP[fn.lower()]
+        for name, c, o in zip(self.agg_names, self.sum_cols, self.agg_ops):
+            if c == col and o == op:
+                return name
+        return None
 
     @staticmethod
     def _split_top(s):
@@ -779,6 +827,44 @@ class GPUAggExecutor(Executor):
             cols[k] = np.array(vals)
         return cols
 
+    def _stage_values(self, batch):
+        """-> (f64 DevColumns of the aggregated columns, per column a host
+        bool mask or None). With null_values=True a column that has nulls
+        is split first (staging.split_nulls), so an int64 column stays
+        exact up to the cast to f64 and what Arrow holds under a null
+        never reaches the device; masks is None otherwise."""
+        _, shim, staging = _lazy_gpu()
+        staged = {}                 # min(b) and max(b) share one upload
+        for c in self.sum_cols:
+            if c in staged:
+                continue
+            col, mask = batch.column(c), None
+            if self.null_values and col.null_count:
+                col, mask = staging.split_nulls(col)
+            staged[c] = (shim.DevColumn.from_numpy(
+                staging.column_to_numpy(col).astype(np.float64)), mask)
+        vcols = [staged[c][0] for c in self.sum_cols]
+        masks = [staged[c][1] for c in self.sum_cols]
+        return vcols, (masks if self.null_values else None)
+
+    def _execute_grand_nullable(self, batch):
+        """null_values=True without keys: the dense accumulate over an
+        all-zero code column, one record and one seen word."""
+        ops, shim, _ = _lazy_gpu()
+        if self._gb is None:
+            self._gb = ops.DenseAcc(len(self.sum_cols), self.agg_ops,
+                                    capacity=1, nullable_vals=True,
+                                    who=type(self).__name__)
+        n = len(batch)
+        codes = shim.DevColumn(np.uint32, n)
+        shim.call("qk_dmemset", codes.ptr, 0, shim.c_u64(n * 4))
+        vcols, masks = self._stage_values(batch)
+        try:
+            self._gb.accumulate(codes, 1, vcols, n, masks)
+        finally:
+            for c in [codes] + list({id(v): v for v in vcols}.values()):
+                c.free()
+
     def execute(self, batches, stream_id, executor_id):
         import pyarrow as pa
         ops, shim, staging = _lazy_gpu()
@@ -788,6 +874,8 @@ class GPUAggExecutor(Executor):
         batch = pa.concat_tables(batches)
         if self.device_keys and self.groupby_keys:
             return self._execute_device_keys(batch)
+        if self.null_values:        # no keys: refused with keys in __init__
+            return self._execute_grand_nullable(batch)
         if self.groupby_keys:
             keys = self._encode_keys(batch)
         else:
@@ -821,36 +909,34 @@ class GPUAggExecutor(Executor):
                 len(self.groupby_keys), len(self.sum_cols),
                 agg_ops=self.agg_ops,
                 expected_groups=max(1024, len(batch)),
-                nullable_keys=self.null_keys)
+                nullable_keys=self.null_keys,
+                **({"nullable_vals": True} if self.null_values else {}))
         kcols = [shim.DevColumn.from_numpy(w) for w in words]
-        vcols = [shim.DevColumn.from_numpy(
-            staging.column_to_numpy(batch.column(c)).astype(np.float64))
-            for c in self.sum_cols]
+        vcols, vmasks = self._stage_values(batch)
         try:
-            self._gb.update(kcols, vcols, len(batch), key_valid=masks)
+            if self.null_values:
+                self._gb.update(kcols, vcols, len(batch), key_valid=masks,
+                                val_valid=vmasks)
+            else:
+                self._gb.update(kcols, vcols, len(batch), key_valid=masks)
         finally:
-            for c in kcols + vcols:
+            for c in kcols + list({id(v): v for v in vcols}.values()):
                 c.free()
 
     def _done_device_keys(self):
         key_words, sums = self._gb.extract()
-        s = {c: sums[i] for i, c in enumerate(self.sum_cols)}
+        s = {c: sums[i] for i, c in enumerate(self.agg_names)}
         kw = self._key_words
         masks = {}
         if self.null_keys:
             masks = dict(zip(self.groupby_keys, self._gb.extract_valid()))
         out = {k: kw.decode(k, w, masks.get(k))
                for k, w in zip(self.groupby_keys, key_words)}
-        for alias, expr in self.exprs:
-            out[alias] = eval(expr, {"s": s})  # noqa: S307 — expr built above
-        # bool keys order as 0/1 (numpy refuses to negate a bool array)
-        order = self._order_by({k: (v.astype(np.uint8)
-                                    if getattr(v, "dtype", None) == np.bool_
-                                    else v) for k, v in out.items()},
-                               masks)
-        if order is not None:
-            out = {k: np.asarray(v)[order] for k, v in out.items()}
-            masks = {k: m[order] for k, m in masks.items()}
+        vals_valid = None
+        if self.null_values:
+            vals_valid = dict(zip(self.agg_names,
+                                  self._gb.extract_vals_valid()))
+        out, masks = self._final_columns(out, s, vals_valid, masks)
         for k in self.groupby_keys:
             out[k] = kw.to_arrow(k, out[k], masks.get(k))
         self._gb.free()
@@ -859,11 +945,58 @@ class GPUAggExecutor(Executor):
         self._key_words = None
         return _to_table(out)
 
+    def _final_columns(self, out, s, vals_valid=None, masks=None):
+        """The host end of done(), no device in it: evaluates the output
+        expressions over the per-group aggregates s (column -> array [G]),
+        adds them to the key columns in `out`, and applies the order-by.
+        -> (columns, masks), both in output order.
+
+        vals_valid (null_values=True): column -> bool array [G], False
+        where that aggregate of the group is NULL. An expression is NULL
+        where any aggregate it references is; identities stand under
+        those slots, so it is evaluated with the floating-point warnings
+        off. An alias that has a NULL joins `masks`, which puts its NULLs
+        last in the order-by, and comes back as an Arrow float64 array
+        with the nulls in place; every other alias comes back as the
+        numpy array it has always been."""
+        import contextlib
+        masks = dict(masks or {})
+        quiet = np.errstate(all="ignore") if vals_valid is not None \
+            else contextlib.nullcontext()
+        nullable = []
+        with quiet:
+            for (alias, expr), refs in zip(self.exprs, self.expr_cols):
+                v = eval(expr, {"s": s})  # noqa: S307 — expr built above
+                if vals_valid is not None:
+                    ok = np.logical_and.reduce([vals_valid[c] for c in refs])
+                    if not ok.all():
+                        # NULL rows tie in the order-by whatever stood there
+                        v = np.where(ok, v, 0.0)
+                        masks[alias] = ok
+                        nullable.append(alias)
+                out[alias] = v
+        # bool keys order as 0/1 (numpy refuses to negate a bool array)
+        order = self._order_by({k: (v.astype(np.uint8)
+                                    if getattr(v, "dtype", None) == np.bool_
+                                    else v) for k, v in out.items()},
+                               masks)
+        if order is not None:
+            out = {k: np.asarray(v)[order] for k, v in out.items()}
+            masks = {k: m[order] for k, m in masks.items()}
+        if nullable:
+            import pyarrow as pa
+            for alias in nullable:
+                out[alias] = pa.array(
+                    np.asarray(out[alias], dtype=np.float64),
+                    type=pa.float64(), mask=~masks[alias])
+        return out, masks
+
     def _order_by(self, out, masks=None):
         """Row order of the order-by clause over the output columns, or
-        None without one. masks: key -> bool array (True = valid) of the
-        null_keys path; the NULLs of such a key sort last, ascending and
-        descending alike."""
+        None without one. masks: column -> bool array (True = valid), the
+        keys of the null_keys path and the aliases of the null_values
+        path that hold a NULL; the NULLs of such a column sort last,
+        ascending and descending alike."""
         if not self.orderby_keys:
             return None
         cols = []
@@ -890,6 +1023,14 @@ class GPUAggExecutor(Executor):
             return None
         if self.device_keys and self.groupby_keys:
             return self._done_device_keys()
+        if self.null_values:
+            sums, valid = self._gb.extract(1), self._gb.extract_valid(1)
+            out, _ = self._final_columns(
+                {}, {c: sums[i] for i, c in enumerate(self.agg_names)},
+                dict(zip(self.agg_names, valid)))
+            self._gb.free()
+            self._gb = None
+            return _to_table(out)
         keys, sums = self._gb.extract()
         s = {c: sums[i] for i, c in enumerate(self.sum_cols)}
         out = {}

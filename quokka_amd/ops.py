@@ -104,8 +104,8 @@ def _pow2_at_least(n):
     return c
 
 
-def _key_bitmap(col, valid, n):
-    """Validity bitmap of a key column for n rows -> (device bitmap or
+def _key_bitmap(col, valid, n, what="key"):
+    """Validity bitmap of a key (or value) column for n rows -> (device bitmap or
     None, owned). `valid` is None, a device bitmap (anything with .ptr, in
     the NullableColumn.valid layout) or a host bool mask (True = valid),
     which is packed and uploaded; with None a NullableColumn supplies its
@@ -117,8 +117,8 @@ def _key_bitmap(col, valid, n):
         return valid, False
     mask = np.asarray(valid)
     if mask.dtype != np.bool_ or mask.ndim != 1 or len(mask) < n:
-        raise TypeError("key validity: a device bitmap or a host bool "
-                        "mask of at least n rows expected")
+        raise TypeError("%s validity: a device bitmap or a host bool "
+                        "mask of at least n rows expected" % what)
     bits = pack_valid(mask[:n])
     buf = DevBuffer(len(bits))
     shim.call("qk_h2d", buf.ptr, bits.ctypes.data_as(c_vp),
@@ -902,26 +902,39 @@ class DeviceKeyDict:
         self._ctr.free()
 
 
-class GroupByKeys:
-    """Group-by over K full-width key columns with nvals f64 SUM/MIN/MAX
-    columns: DeviceKeyDict codes, then one dense accumulate into the
-    record of each row's code (SQLAggExecutor's DuckDB group-by over an
-    arbitrary groupby_keys list, sql_executors.py:556-599). Because codes
-    are dense the accumulate needs no second hash walk and extract() no
-    compaction. Growth is internal; the group limit is 2**31 - 1.
-    nullable_keys=True makes NULL a group, one per null pattern across the
-    keys (DeviceKeyDict(nullable=True)); extract_valid() says where."""
+class DenseAcc:
+    """The accumulator half of GroupByKeys: one record of rstride (pow2 >=
+    nvals) f64 words per dense code, SUM/MIN/MAX per agg_ops, growth by
+    device copy, accumulate by a column of codes. The codes come from a
+    DeviceKeyDict (GroupByKeys) or from the caller: the grand aggregate of
+    GPUAggExecutor(null_values=True) runs it over an all-zero code column
+    with one code.
+
+    nullable_vals=True admits SQL NULLs among the values (DESIGN.md
+    §3a''''): accumulate() then takes one validity per value column and
+    launches qk_groupby_dense_acc_valid, a `seen` column beside the
+    records (one u64 per code, bit c set once value column c of that code
+    has received a value) grows with them, and extract_valid() says which
+    aggregates are NULL. The bits of one word cap this at 64 value
+    columns. With the default the launches are those of
+    qk_groupby_dense_acc alone."""
 
     AGG_INIT = GroupByI64.AGG_INIT
+    MAX_NULLABLE_VALS = 64
 
-    def __init__(self, nkeys, nvals, agg_ops=None, expected_groups=1024,
-                 stream=None, nullable_keys=False):
+    def __init__(self, nvals, agg_ops=None, capacity=1024, stream=None,
+                 nullable_vals=False, who="DenseAcc"):
         self.nvals = int(nvals)
         self.agg_ops = list(agg_ops) if agg_ops else [0] * self.nvals
         assert len(self.agg_ops) == self.nvals
+        self.nullable_vals = bool(nullable_vals)
+        self.who = who
+        if self.nullable_vals and self.nvals > self.MAX_NULLABLE_VALS:
+            raise ValueError(
+                "%s: nullable_vals=True takes at most %d value columns "
+                "(one bit each of a group's seen word), got %d"
+                % (who, self.MAX_NULLABLE_VALS, self.nvals))
         self.stream = stream
-        self.dict = DeviceKeyDict(nkeys, expected_groups, stream,
-                                  nullable=nullable_keys)
         self.rstride = _pow2_at_least(max(1, self.nvals))
         self._inits_dev = DevColumn.from_numpy(
             np.asarray([self.AGG_INIT[op] for op in self.agg_ops] or [0.0],
@@ -932,13 +945,13 @@ class GroupByKeys:
                 np.asarray(self.agg_ops, dtype=np.int32))
         self._err = DevBuffer(4)
         shim.call("qk_dmemset", self._err.ptr, 0, c_u64(4))
-        self.acc_cap = max(1, int(expected_groups))
-        self.acc = DevColumn(np.float64, self.acc_cap * self.rstride)
-        self._init_records(self.acc, 0, self.acc_cap)
-
-    @property
-    def n_groups(self):
-        return self.dict.n_codes
+        self.cap = max(1, int(capacity))
+        self.acc = DevColumn(np.float64, self.cap * self.rstride)
+        self._init_records(self.acc, 0, self.cap)
+        self.seen = None
+        if self.nullable_vals:
+            self.seen = DevColumn(np.uint64, self.cap)
+            shim.call("qk_dmemset", self.seen.ptr, 0, c_u64(self.cap * 8))
 
     def _init_records(self, acc, first, count):
         sh = self.stream.handle if self.stream else None
@@ -948,83 +961,221 @@ class GroupByKeys:
 
     def _grow_acc(self, need):
         """Records of existing codes move by device copy; the new capacity
-        starts at the op identities."""
+        starts at the op identities, and its seen words at 0."""
         new_cap = _pow2_at_least(2 * need)
         new = DevColumn(np.float64, new_cap * self.rstride)
         sh = self.stream.handle if self.stream else None
         shim.call("qk_stream_sync", sh)
         shim.call("qk_d2d", new.ptr, self.acc.ptr,
-                  c_u64(self.acc_cap * self.rstride * 8))
-        self._init_records(new, self.acc_cap, new_cap - self.acc_cap)
+                  c_u64(self.cap * self.rstride * 8))
+        self._init_records(new, self.cap, new_cap - self.cap)
+        new_seen = None
+        if self.seen is not None:
+            new_seen = DevColumn(np.uint64, new_cap)
+            shim.call("qk_d2d", new_seen.ptr, self.seen.ptr,
+                      c_u64(self.cap * 8))
+            shim.call("qk_dmemset",
+                      shim.c_vp(new_seen.ptr.value + self.cap * 8), 0,
+                      c_u64((new_cap - self.cap) * 8))
         shim.call("qk_stream_sync", sh)
         self.acc.free()
         self.acc = new
-        self.acc_cap = new_cap
+        if new_seen is not None:
+            self.seen.free()
+            self.seen = new_seen
+        self.cap = new_cap
 
-    def update(self, key_cols, val_cols, n=None, key_valid=None):
-        """key_valid: one validity entry per key, as DeviceKeyDict.encode's
-        `valid` (nullable_keys=True only)."""
+    def check_vals(self, val_cols, n, val_valid):
+        """Host-only argument checks of accumulate(), for callers that
+        must refuse before any device work of their own."""
         assert len(val_cols) == self.nvals
-        n = min(c.n for c in key_cols) if n is None else int(n)
-        if not n:
-            return
         for v in val_cols:
             if v.dtype != np.dtype(np.float64) or v.n < n:
-                raise TypeError("GroupByKeys.update: value columns are "
-                                "float64 with at least n rows")
-        if key_valid is None:
-            codes = self.dict.encode(key_cols, n)
-        else:
-            codes = self.dict.encode(key_cols, n, valid=key_valid)
-        try:
-            if not self.nvals:
-                return
-            if self.dict.n_codes > self.acc_cap:
-                self._grow_acc(self.dict.n_codes)
-            sh = self.stream.handle if self.stream else None
-            dptrs = _dev_ptr_array(val_cols)
-            shim.call("qk_groupby_dense_acc", sh, c_u64(n), codes.ptr,
-                      c_u32(self.dict.n_codes), dptrs.ptr,
-                      self._ops_dev.ptr if self._ops_dev else None,
-                      self.nvals, self.rstride, self.acc.ptr, self._err.ptr)
-            shim.call("qk_stream_sync", sh)
-            dptrs.free()
-            err = np.zeros(1, dtype=np.uint32)
-            shim.call("qk_d2h", err.ctypes.data_as(c_vp), self._err.ptr,
-                      c_u64(4))
-            if err[0]:
-                raise RuntimeError("GroupByKeys.update: a code lay beyond "
-                                   "the accumulator records (device error "
-                                   "word %d)" % int(err[0]))
-        finally:
-            codes.free()
+                raise TypeError("%s.update: value columns are float64 with "
+                                "at least n rows" % self.who)
+        if self.nullable_vals:
+            if val_valid is not None and len(val_valid) != self.nvals:
+                raise ValueError("%s.update: %d value validity entries, "
+                                 "expected %d" % (self.who, len(val_valid),
+                                                  self.nvals))
+        elif val_valid is not None or any(isinstance(v, NullableColumn)
+                                          for v in val_cols):
+            raise TypeError("%s.update: val_valid= or a NullableColumn "
+                            "value needs a table made with "
+                            "nullable_vals=True" % self.who)
 
-    def extract(self):
-        """-> (list of K np.int64 key-word arrays [G], sums np.float64
-        [nvals, G]); row g of every array belongs to code g."""
-        g = self.dict.n_codes
-        keys = self.dict.keys_host()
+    def accumulate(self, codes, ncodes, val_cols, n, val_valid=None):
+        """Row i of the value columns goes into the record of codes[i]
+        (u32 DevColumn, every code < ncodes). val_valid (nullable_vals=True
+        only): one entry per value column, a device bitmap in the
+        NullableColumn.valid layout, a host bool mask (True = valid) or
+        None for a column without nulls; a NullableColumn among val_cols
+        supplies its own bitmap."""
+        self.check_vals(val_cols, n, val_valid)
+        if not n or not self.nvals:
+            return
+        if ncodes > self.cap:
+            self._grow_acc(ncodes)
+        sh = self.stream.handle if self.stream else None
+        ops_ptr = self._ops_dev.ptr if self._ops_dev else None
+        tmp = []
+        try:
+            dptrs = _dev_ptr_array(val_cols)
+            tmp.append(dptrs)
+            if not self.nullable_vals:
+                shim.call("qk_groupby_dense_acc", sh, c_u64(n), codes.ptr,
+                          c_u32(ncodes), dptrs.ptr, ops_ptr, self.nvals,
+                          self.rstride, self.acc.ptr, self._err.ptr)
+            else:
+                bitmaps = []
+                for c, v in zip(val_cols, val_valid or [None] * self.nvals):
+                    bm, owned = _key_bitmap(c, v, n, "value")
+                    if owned:
+                        tmp.append(bm)
+                    bitmaps.append(0 if bm is None else
+                                   getattr(bm.ptr, "value", bm.ptr) or 0)
+                vptrs = DevColumn.from_numpy(
+                    np.array(bitmaps, dtype=np.uint64))
+                tmp.append(vptrs)
+                shim.call("qk_groupby_dense_acc_valid", sh, c_u64(n),
+                          codes.ptr, c_u32(ncodes), dptrs.ptr, vptrs.ptr,
+                          ops_ptr, self.nvals, self.rstride, self.acc.ptr,
+                          self.seen.ptr, self._err.ptr)
+            shim.call("qk_stream_sync", sh)
+        finally:
+            for t in tmp:
+                t.free()
+        err = np.zeros(1, dtype=np.uint32)
+        shim.call("qk_d2h", err.ctypes.data_as(c_vp), self._err.ptr,
+                  c_u64(4))
+        if err[0]:
+            raise RuntimeError("%s.update: a code lay beyond the "
+                               "accumulator records (device error word %d)"
+                               % (self.who, int(err[0])))
+
+    def extract(self, g):
+        """-> np.float64 [nvals, g], column i the record of code i. An
+        aggregate that met no value holds its op identity."""
         recs = np.empty(g * self.rstride, dtype=np.float64)
         if g and self.nvals:
             shim.call("qk_stream_sync",
                       self.stream.handle if self.stream else None)
             shim._bounce.d2h(recs, self.acc.ptr)
-        sums = np.ascontiguousarray(
+        return np.ascontiguousarray(
             recs.reshape(g, self.rstride)[:, :self.nvals].T)
-        return keys, sums
+
+    def extract_valid(self, g):
+        """-> bool [nvals, g], False where that aggregate of code i is
+        NULL (none of its inputs was a value)."""
+        if not self.nullable_vals:
+            raise TypeError("%s.extract_vals_valid: the table was not made "
+                            "with nullable_vals=True" % self.who)
+        words = np.empty(g, dtype=np.uint64)
+        if g:
+            shim.call("qk_stream_sync",
+                      self.stream.handle if self.stream else None)
+            shim._bounce.d2h(words, self.seen.ptr)
+        bits = np.arange(self.nvals, dtype=np.uint64)[:, None]
+        return ((words[None, :] >> bits) & np.uint64(1)).astype(bool)
+
+    def free(self):
+        self.acc.free()
+        if self.seen is not None:
+            self.seen.free()
+        self._inits_dev.free()
+        self._err.free()
+        if self._ops_dev is not None:
+            self._ops_dev.free()
+
+
+class GroupByKeys:
+    """Group-by over K full-width key columns with nvals f64 SUM/MIN/MAX
+    columns: DeviceKeyDict codes, then one dense accumulate into the
+    record of each row's code (SQLAggExecutor's DuckDB group-by over an
+    arbitrary groupby_keys list, sql_executors.py:556-599). Because codes
+    are dense the accumulate needs no second hash walk and extract() no
+    compaction. Growth is internal; the group limit is 2**31 - 1.
+    nullable_keys=True makes NULL a group, one per null pattern across the
+    keys (DeviceKeyDict(nullable=True)); extract_valid() says where.
+    nullable_vals=True lets the value columns hold NULLs, which SUM / MIN /
+    MAX skip (DenseAcc); extract_vals_valid() says which aggregates met no
+    value and are NULL."""
+
+    AGG_INIT = GroupByI64.AGG_INIT
+
+    def __init__(self, nkeys, nvals, agg_ops=None, expected_groups=1024,
+                 stream=None, nullable_keys=False, nullable_vals=False):
+        self.nvals = int(nvals)
+        self.agg_ops = list(agg_ops) if agg_ops else [0] * self.nvals
+        assert len(self.agg_ops) == self.nvals
+        if nullable_vals and self.nvals > DenseAcc.MAX_NULLABLE_VALS:
+            raise ValueError(
+                "GroupByKeys: nullable_vals=True takes at most %d value "
+                "columns (one bit each of a group's seen word), got %d"
+                % (DenseAcc.MAX_NULLABLE_VALS, self.nvals))
+        self.stream = stream
+        self.nullable_vals = bool(nullable_vals)
+        self.dict = DeviceKeyDict(nkeys, expected_groups, stream,
+                                  nullable=nullable_keys)
+        self._acc = DenseAcc(self.nvals, self.agg_ops, expected_groups,
+                             stream, nullable_vals, who="GroupByKeys")
+
+    @property
+    def n_groups(self):
+        return self.dict.n_codes
+
+    @property
+    def rstride(self):
+        return self._acc.rstride
+
+    @property
+    def acc_cap(self):
+        return self._acc.cap
+
+    def update(self, key_cols, val_cols, n=None, key_valid=None,
+               val_valid=None):
+        """key_valid: one validity entry per key, as DeviceKeyDict.encode's
+        `valid` (nullable_keys=True only). val_valid: one per value column
+        in the same forms (nullable_vals=True only); a NullableColumn among
+        val_cols supplies its own."""
+        assert len(val_cols) == self.nvals
+        n = min(c.n for c in key_cols) if n is None else int(n)
+        if not n:
+            return
+        self._acc.check_vals(val_cols, n, val_valid)
+        if key_valid is None:
+            codes = self.dict.encode(key_cols, n)
+        else:
+            codes = self.dict.encode(key_cols, n, valid=key_valid)
+        try:
+            self._acc.accumulate(codes, self.dict.n_codes, val_cols, n,
+                                 val_valid)
+        finally:
+            codes.free()
+
+    def extract(self):
+        """-> (list of K np.int64 key-word arrays [G], sums np.float64
+        [nvals, G]); row g of every array belongs to code g. An aggregate
+        that extract_vals_valid() calls NULL holds its op identity (0,
+        +inf, -inf)."""
+        g = self.dict.n_codes
+        keys = self.dict.keys_host()
+        return keys, self._acc.extract(g)
 
     def extract_valid(self):
         """-> list of K bool arrays [G], False where that key of group g is
         NULL; row g belongs to code g, as in extract()."""
         return self.dict.keys_valid_host()
 
+    def extract_vals_valid(self):
+        """-> bool array [nvals, G], False where that aggregate of group g
+        is NULL: every input it was given was NULL (nullable_vals=True
+        only). Row g belongs to code g, as in extract()."""
+        return self._acc.extract_valid(self.dict.n_codes)
+
     def free(self):
         self.dict.free()
-        self.acc.free()
-        self._inits_dev.free()
-        self._err.free()
-        if self._ops_dev is not None:
-            self._ops_dev.free()
+        self._acc.free()
 
 
 class StringColumn:

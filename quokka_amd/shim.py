@@ -161,6 +161,9 @@ _SIGS = {
                               ctypes.c_int, c_vp],
     "qk_groupby_dense_acc": [c_vp, c_u64, c_vp, c_u32, c_vp, c_vp,
                              ctypes.c_int, ctypes.c_int, c_vp, c_vp],
+    "qk_groupby_dense_acc_valid": [c_vp, c_u64, c_vp, c_u32, c_vp, c_vp,
+                                   c_vp, ctypes.c_int, ctypes.c_int, c_vp,
+                                   c_vp, c_vp],
     "qk_str_like_i32": [c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.c_int, c_vp],
     "qk_str_like_i64": [c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.c_int, c_vp],
     "qk_str_like_path_i32": [c_vp, c_u64, c_vp, c_vp, c_vp, ctypes.c_int,
