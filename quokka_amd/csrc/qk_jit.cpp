@@ -108,6 +108,8 @@ static std::string gen_source(const char *expr, int ncols,
        "      counts[b] = acc; acc += c; }\n"
        "    *total = acc;\n  }\n}\n";
 
+  // the step loop below mirrors compact_step / k_compact_scatter of
+  // quokka_amd.hip, which a hiprtc source string cannot include
   s += "extern \"C\" __global__ __launch_bounds__(BLOCK) void jit_scatter(\n";
   s += "    u64 n, u64 chunk, const u64* block_offsets, u32* out_idx";
   for (int c = 0; c < ncols; c++) {

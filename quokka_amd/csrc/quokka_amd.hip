@@ -774,32 +774,47 @@ extern "C" int qk_q6_agg(void *stream, uint64_t n, const int32_t *shipdate,
   return 0;
 }
 
-// ---- generic filter (ordered compaction) ------------------------------
+// ---- ordered compaction (filter, Q3 extract, newline index) ------------
 // Three launches: per-block count over contiguous chunks -> single-block
-// exclusive scan of block counts -> re-evaluate + rank + scatter. Row order
-// is preserved (polars filter semantics, core.py:170).
+// exclusive scan of block counts -> re-evaluate + rank + scatter. Element
+// order is preserved (polars filter semantics, core.py:170). One skeleton,
+// instantiated with pred(i) "is element i live" and emit(i, pos) "write it
+// as output pos"; qk_valid_expand, the inverse, runs compact_step from a
+// kernel of its own.
 
-template <typename T>
-__device__ inline bool cmp_op(T v, int op, T ref) {
-  switch (op) {
-  case 0: return v < ref;
-  case 1: return v <= ref;
-  case 2: return v > ref;
-  case 3: return v >= ref;
-  case 4: return v == ref;
-  default: return v != ref;
+// One BLOCK-element step. `mask` is the wave's word of live lanes (a
+// __ballot, or a validity bitmap word). Returns base + live lanes of the
+// earlier waves + live lanes below this one, which is the output position
+// of a live lane, and advances `base`, which every thread carries, by the
+// block's total. Holds two __syncthreads(): all threads of a block call it
+// the same number of times.
+__device__ inline uint64_t compact_step(uint64_t mask, uint64_t &base) {
+  __shared__ uint32_t wave_tot[BLOCK / WAVE];
+  int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+  if (lane == 0) wave_tot[wid] = __popcll(mask);
+  __syncthreads();
+  uint32_t wbase = 0, btot = 0;
+  for (int w = 0; w < BLOCK / WAVE; w++) {
+    uint32_t t = wave_tot[w];
+    if (w < wid) wbase += t;
+    btot += t;
   }
+  __syncthreads();  // the next step writes wave_tot again
+  uint64_t pos = base + wbase + __popcll(mask & ((1ULL << lane) - 1));
+  base += btot;
+  return pos;
 }
 
-template <typename T>
-__global__ void __launch_bounds__(BLOCK) k_filter_count(
-    uint64_t n, const T *__restrict__ col, int op, T ref, uint64_t chunk,
-    uint64_t *__restrict__ block_counts) {
-  uint64_t lo = (uint64_t)blockIdx.x * chunk;
+// block b owns elements [lo0 + b * chunk, min(n, lo0 + (b + 1) * chunk))
+template <typename Pred>
+__global__ void __launch_bounds__(BLOCK) k_compact_count(
+    uint64_t lo0, uint64_t n, uint64_t chunk,
+    uint64_t *__restrict__ block_counts, Pred pred) {
+  uint64_t lo = lo0 + (uint64_t)blockIdx.x * chunk;
   uint64_t hi = qk_min_u64(n, lo + chunk);
   uint32_t cnt = 0;
   for (uint64_t r = lo + threadIdx.x; r < hi; r += BLOCK)
-    cnt += cmp_op(col[r], op, ref) ? 1u : 0u;
+    cnt += pred(r) ? 1u : 0u;
   uint64_t s = block_sum(cnt);
   if (threadIdx.x == 0) block_counts[blockIdx.x] = s;
 }
@@ -818,61 +833,88 @@ __global__ void k_scan_blocks(uint64_t nblocks, uint64_t *__restrict__ counts,
   }
 }
 
-template <typename T>
-__global__ void __launch_bounds__(BLOCK) k_filter_scatter(
-    uint64_t n, const T *__restrict__ col, int op, T ref, uint64_t chunk,
-    const uint64_t *__restrict__ block_offsets, uint32_t *__restrict__ out_idx) {
-  uint64_t lo = (uint64_t)blockIdx.x * chunk;
+template <typename Pred, typename Emit>
+__global__ void __launch_bounds__(BLOCK) k_compact_scatter(
+    uint64_t lo0, uint64_t n, uint64_t chunk,
+    const uint64_t *__restrict__ block_offsets, Pred pred, Emit emit) {
+  uint64_t lo = lo0 + (uint64_t)blockIdx.x * chunk;
   uint64_t hi = qk_min_u64(n, lo + chunk);
-  __shared__ uint64_t base;
-  __shared__ uint32_t wave_tot[BLOCK / WAVE];
-  if (threadIdx.x == 0) base = block_offsets[blockIdx.x];
-  __syncthreads();
-  int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+  uint64_t base = block_offsets[blockIdx.x];
   for (uint64_t r0 = lo; r0 < hi; r0 += BLOCK) {
     uint64_t r = r0 + threadIdx.x;
-    bool pass = r < hi && cmp_op(col[r], op, ref);
-    uint64_t mask = __ballot(pass);
-    uint32_t rank = __popcll(mask & ((1ULL << lane) - 1));
-    uint32_t wtot = __popcll(mask);
-    if (lane == 0) wave_tot[wid] = wtot;
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (int w = 0; w < wid; w++) wbase += wave_tot[w];
-    if (pass) out_idx[base + wbase + rank] = (uint32_t)r;
-    uint32_t btot = 0;
-    for (int w = 0; w < BLOCK / WAVE; w++) btot += wave_tot[w];
-    __syncthreads();
-    if (threadIdx.x == 0) base += btot;
-    __syncthreads();
+    bool live = r < hi && pred(r);
+    uint64_t pos = compact_step(__ballot(live), base);
+    if (live) emit(r, pos);
   }
 }
+
+// chunks of a multiple of BLOCK elements, at most MAX_BLOCKS of them
+static uint32_t qk_compact_blocks(uint64_t n, uint64_t *chunk) {
+  uint64_t c = (n + MAX_BLOCKS - 1) / MAX_BLOCKS;
+  c = ((c + BLOCK - 1) / BLOCK) * BLOCK;
+  *chunk = c;
+  return (uint32_t)((n + c - 1) / c);
+}
+
+// Compacts the live elements of [lo0, n), n > lo0; their count lands in
+// *total_dev. The block counts live in one per-thread buffer PER
+// INSTANTIATION, so two entry points never share one. Two launches of the
+// same entry point on two streams of one thread still do (a known hazard).
+template <typename Pred, typename Emit>
+static int qk_compact(const char *who, void *stream, uint64_t lo0, uint64_t n,
+                      uint64_t *total_dev, Pred pred, Emit emit) {
+  uint64_t chunk;
+  uint32_t blocks = qk_compact_blocks(n - lo0, &chunk);
+  static __thread uint64_t *scratch = nullptr;
+  if (!scratch)
+    QK_TRY(who, hipMalloc(&scratch, MAX_BLOCKS * sizeof(uint64_t)));
+  hipLaunchKernelGGL(k_compact_count<Pred>, dim3(blocks), dim3(BLOCK), 0,
+                     (hipStream_t)stream, lo0, n, chunk, scratch, pred);
+  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1), 0, (hipStream_t)stream,
+                     (uint64_t)blocks, scratch, total_dev);
+  hipLaunchKernelGGL((k_compact_scatter<Pred, Emit>), dim3(blocks),
+                     dim3(BLOCK), 0, (hipStream_t)stream, lo0, n, chunk,
+                     scratch, pred, emit);
+  QK_TRY(who, hipGetLastError());
+  return 0;
+}
+
+// ---- generic filter ----------------------------------------------------
+template <typename T>
+__device__ inline bool cmp_op(T v, int op, T ref) {
+  switch (op) {
+  case 0: return v < ref;
+  case 1: return v <= ref;
+  case 2: return v > ref;
+  case 3: return v >= ref;
+  case 4: return v == ref;
+  default: return v != ref;
+  }
+}
+
+template <typename T>
+struct FilterPred {
+  const T *__restrict__ col;
+  int op;
+  T ref;
+  __device__ bool operator()(uint64_t r) const {
+    return cmp_op(col[r], op, ref);
+  }
+};
+struct EmitRowU32 {
+  uint32_t *__restrict__ out_idx;
+  __device__ void operator()(uint64_t r, uint64_t pos) const {
+    out_idx[pos] = (uint32_t)r;
+  }
+};
 
 template <typename T>
 static int qk_filter_impl(const char *who, void *stream, uint64_t n,
                           const T *col, int op, T value, uint32_t *out_idx,
                           uint64_t *out_count_dev) {
   if (!n) return 0;
-  uint64_t rows_per_block = (n + MAX_BLOCKS - 1) / MAX_BLOCKS;
-  rows_per_block = ((rows_per_block + BLOCK - 1) / BLOCK) * BLOCK;
-  uint32_t blocks = (uint32_t)((n + rows_per_block - 1) / rows_per_block);
-  static __thread uint64_t *scratch = nullptr;  // per-thread block_counts buf
-  static __thread uint64_t scratch_cap = 0;
-  if (scratch_cap < blocks) {
-    if (scratch) hipFree(scratch);
-    QK_TRY(who, hipMalloc(&scratch, (MAX_BLOCKS + 1) * sizeof(uint64_t)));
-    scratch_cap = MAX_BLOCKS + 1;
-  }
-  hipLaunchKernelGGL(k_filter_count<T>, dim3(blocks), dim3(BLOCK), 0,
-                     (hipStream_t)stream, n, col, op, value, rows_per_block,
-                     scratch);
-  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1), 0, (hipStream_t)stream,
-                     (uint64_t)blocks, scratch, out_count_dev);
-  hipLaunchKernelGGL(k_filter_scatter<T>, dim3(blocks), dim3(BLOCK), 0,
-                     (hipStream_t)stream, n, col, op, value, rows_per_block,
-                     scratch, out_idx);
-  QK_TRY(who, hipGetLastError());
-  return 0;
+  return qk_compact(who, stream, 0, n, out_count_dev,
+                    FilterPred<T>{col, op, value}, EmitRowU32{out_idx});
 }
 extern "C" int qk_filter_i32(void *stream, uint64_t n, const int32_t *col,
                              int op, int32_t value, uint32_t *out_idx,
@@ -1050,13 +1092,30 @@ __device__ inline bool bloom_test(const uint32_t *bloom, uint64_t bloom_mask,
   return (bloom[w] & m) == m;
 }
 
-__global__ void __launch_bounds__(BLOCK) k_join_build2(
-    uint64_t n, const int64_t *__restrict__ keys, uint32_t row_offset,
+// ---- join build / probe, with or without a validity bitmap ------------
+// SQL: a NULL key equals nothing, on either side (polars join,
+// sql_executors.py:371). `valid` is the key column's Arrow validity bitmap
+// (include/quokka_amd.h, nullable columns); whatever the key column holds
+// under a null is never read. HAS_VALID = false is the kernel of the
+// no-bitmap entry points: `valid` is then a null pointer nothing reads.
+__device__ inline bool qk_valid_bit(const uint8_t *__restrict__ valid,
+                                    uint64_t i) {
+  return (valid[i >> 3] >> (i & 7)) & 1;
+}
+
+// A null build row takes no slot and no chain link but keeps its row
+// number, so build indices still address the payload columns.
+template <bool HAS_VALID>
+__global__ void __launch_bounds__(BLOCK) k_join_build(
+    uint64_t n, const int64_t *__restrict__ keys,
+    const uint8_t *__restrict__ valid, uint32_t row_offset,
     int64_t *__restrict__ slot_keys, int32_t *__restrict__ slot_head,
     int32_t *__restrict__ chain_next, uint64_t cap) {
   uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
+    if constexpr (HAS_VALID)
+      if (!qk_valid_bit(valid, i)) continue;
     uint64_t s = ht_find_or_insert(slot_keys, cap, keys[i]);
     int32_t me = (int32_t)(row_offset + i);
     int32_t old = atomicExch(&slot_head[s], me);
@@ -1070,16 +1129,36 @@ extern "C" int qk_join_build(void *stream, uint64_t n, const int64_t *keys,
                              uint64_t cap) {
   if (!n) return 0;
   if (!qk_pow2(cap)) return qk_fail("qk_join_build.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks = qk_grid(n);
-  hipLaunchKernelGGL(k_join_build2, dim3(blocks), dim3(BLOCK), 0,
-                     (hipStream_t)stream, n, keys, row_offset, slot_keys,
-                     slot_head, chain_next, cap);
+  hipLaunchKernelGGL(k_join_build<false>, dim3(qk_grid(n)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, n, keys, (const uint8_t *)nullptr,
+                     row_offset, slot_keys, slot_head, chain_next, cap);
   QK_TRY("qk_join_build", hipGetLastError());
   return 0;
 }
+extern "C" int qk_join_build_valid(void *stream, uint64_t n,
+                                   const int64_t *keys,
+                                   const uint64_t *valid_dev,
+                                   uint32_t row_offset, int64_t *slot_keys,
+                                   int32_t *slot_head, int32_t *chain_next,
+                                   uint64_t cap) {
+  if (!n) return 0;
+  if (!qk_pow2(cap))
+    return qk_fail("qk_join_build_valid.cap_pow2", hipErrorInvalidValue);
+  if (!valid_dev)
+    return qk_fail("qk_join_build_valid.valid_null", hipErrorInvalidValue);
+  hipLaunchKernelGGL(k_join_build<true>, dim3(qk_grid(n)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, n, keys, (const uint8_t *)valid_dev,
+                     row_offset, slot_keys, slot_head, chain_next, cap);
+  QK_TRY("qk_join_build_valid", hipGetLastError());
+  return 0;
+}
 
+// A null probe row is a miss without a walk: nothing for inner and semi,
+// emitted for anti.
+template <bool HAS_VALID>
 __global__ void __launch_bounds__(BLOCK) k_join_probe(
     uint64_t n, const int64_t *__restrict__ keys,
+    const uint8_t *__restrict__ valid,
     const int64_t *__restrict__ slot_keys, const int32_t *__restrict__ slot_head,
     const int32_t *__restrict__ chain_next, uint64_t cap, int mode,
     uint32_t *__restrict__ out_probe, uint32_t *__restrict__ out_build,
@@ -1087,16 +1166,12 @@ __global__ void __launch_bounds__(BLOCK) k_join_probe(
   uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
-    int32_t head = probe_unique(slot_keys, slot_head, cap, keys[i], nullptr);
-    if (mode == 1) {  // semi
-      if (head >= 0) {
-        uint64_t pos = atomicAdd((unsigned long long *)cursor, 1ULL);
-        if (pos < out_cap) out_probe[pos] = (uint32_t)i;
-      }
-      continue;
-    }
-    if (mode == 2) {  // anti
-      if (head < 0) {
+    bool null_key = false;
+    if constexpr (HAS_VALID) null_key = !qk_valid_bit(valid, i);
+    int32_t head = null_key ? -1 : probe_unique(slot_keys, slot_head, cap,
+                                                keys[i], nullptr);
+    if (mode != 0) {  // semi emits hits, anti emits misses
+      if ((head >= 0) == (mode == 1)) {
         uint64_t pos = atomicAdd((unsigned long long *)cursor, 1ULL);
         if (pos < out_cap) out_probe[pos] = (uint32_t)i;
       }
@@ -1123,96 +1198,12 @@ extern "C" int qk_join_probe(void *stream, uint64_t n, const int64_t *keys,
                              uint64_t out_cap, uint64_t *cursor) {
   if (!n) return 0;
   if (!qk_pow2(cap)) return qk_fail("qk_join_probe.cap_pow2", hipErrorInvalidValue);
-  uint32_t blocks = qk_grid(n);
-  hipLaunchKernelGGL(k_join_probe, dim3(blocks), dim3(BLOCK), 0,
-                     (hipStream_t)stream, n, keys, slot_keys, slot_head,
-                     chain_next, cap, mode, out_probe, out_build, out_cap,
-                     cursor);
+  hipLaunchKernelGGL(k_join_probe<false>, dim3(qk_grid(n)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, n, keys, (const uint8_t *)nullptr,
+                     slot_keys, slot_head, chain_next, cap, mode, out_probe,
+                     out_build, out_cap, cursor);
   QK_TRY("qk_join_probe", hipGetLastError());
   return 0;
-}
-
-// ---- join over a nullable key column -----------------------------------
-// SQL: a NULL key equals nothing, on either side (polars join,
-// sql_executors.py:371). `valid` is the key column's Arrow validity bitmap
-// (include/quokka_amd.h, nullable columns); whatever the key column holds
-// under a null is never read. k_join_build2 and k_join_probe above stay
-// the kernels of the no-bitmap entry points.
-__device__ inline bool qk_valid_bit(const uint8_t *__restrict__ valid,
-                                    uint64_t i) {
-  return (valid[i >> 3] >> (i & 7)) & 1;
-}
-
-// A null build row takes no slot and no chain link but keeps its row
-// number, so build indices still address the payload columns.
-__global__ void __launch_bounds__(BLOCK) k_join_build_valid(
-    uint64_t n, const int64_t *__restrict__ keys,
-    const uint8_t *__restrict__ valid, uint32_t row_offset,
-    int64_t *__restrict__ slot_keys, int32_t *__restrict__ slot_head,
-    int32_t *__restrict__ chain_next, uint64_t cap) {
-  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride) {
-    if (!qk_valid_bit(valid, i)) continue;
-    uint64_t s = ht_find_or_insert(slot_keys, cap, keys[i]);
-    int32_t me = (int32_t)(row_offset + i);
-    int32_t old = atomicExch(&slot_head[s], me);
-    chain_next[me] = old;
-  }
-}
-
-extern "C" int qk_join_build_valid(void *stream, uint64_t n,
-                                   const int64_t *keys,
-                                   const uint64_t *valid_dev,
-                                   uint32_t row_offset, int64_t *slot_keys,
-                                   int32_t *slot_head, int32_t *chain_next,
-                                   uint64_t cap) {
-  if (!n) return 0;
-  if (!qk_pow2(cap))
-    return qk_fail("qk_join_build_valid.cap_pow2", hipErrorInvalidValue);
-  if (!valid_dev)
-    return qk_fail("qk_join_build_valid.valid_null", hipErrorInvalidValue);
-  hipLaunchKernelGGL(k_join_build_valid, dim3(qk_grid(n)), dim3(BLOCK), 0,
-                     (hipStream_t)stream, n, keys, (const uint8_t *)valid_dev,
-                     row_offset, slot_keys, slot_head, chain_next, cap);
-  QK_TRY("qk_join_build_valid", hipGetLastError());
-  return 0;
-}
-
-// A null probe row is a miss without a walk: nothing for inner and semi,
-// emitted for anti.
-__global__ void __launch_bounds__(BLOCK) k_join_probe_valid(
-    uint64_t n, const int64_t *__restrict__ keys,
-    const uint8_t *__restrict__ valid,
-    const int64_t *__restrict__ slot_keys, const int32_t *__restrict__ slot_head,
-    const int32_t *__restrict__ chain_next, uint64_t cap, int mode,
-    uint32_t *__restrict__ out_probe, uint32_t *__restrict__ out_build,
-    uint64_t out_cap, uint64_t *__restrict__ cursor) {
-  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride) {
-    int32_t head = -1;
-    if (qk_valid_bit(valid, i))
-      head = probe_unique(slot_keys, slot_head, cap, keys[i], nullptr);
-    if (mode != 0) {  // semi emits hits, anti emits misses
-      if ((head >= 0) == (mode == 1)) {
-        uint64_t pos = atomicAdd((unsigned long long *)cursor, 1ULL);
-        if (pos < out_cap) out_probe[pos] = (uint32_t)i;
-      }
-      continue;
-    }
-    if (head < 0) continue;
-    uint32_t cnt = 0;
-    for (int32_t b = head; b >= 0; b = chain_next[b]) cnt++;
-    uint64_t pos = atomicAdd((unsigned long long *)cursor, (unsigned long long)cnt);
-    for (int32_t b = head; b >= 0; b = chain_next[b]) {
-      if (pos < out_cap) {
-        out_probe[pos] = (uint32_t)i;
-        out_build[pos] = (uint32_t)b;
-      }
-      pos++;
-    }
-  }
 }
 extern "C" int qk_join_probe_valid(void *stream, uint64_t n,
                                    const int64_t *keys,
@@ -1228,7 +1219,7 @@ extern "C" int qk_join_probe_valid(void *stream, uint64_t n,
     return qk_fail("qk_join_probe_valid.cap_pow2", hipErrorInvalidValue);
   if (!valid_dev || mode < 0 || mode > 2 || (mode == 0 && !out_build))
     return qk_fail("qk_join_probe_valid.args", hipErrorInvalidValue);
-  hipLaunchKernelGGL(k_join_probe_valid, dim3(qk_grid(n)), dim3(BLOCK), 0,
+  hipLaunchKernelGGL(k_join_probe<true>, dim3(qk_grid(n)), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, keys, (const uint8_t *)valid_dev,
                      slot_keys, slot_head, chain_next, cap, mode, out_probe,
                      out_build, out_cap, cursor);
@@ -1581,56 +1572,29 @@ extern "C" int qk_q3_probe_agg_nt(void *stream, uint64_t n,
 // Two passes over contiguous slot chunks (per-block count -> single-block
 // scan -> rank+scatter): no shared cursor word (a single cursor measured
 // 8.6 ms on 1.2M groups; wave-aggregated claims still 5.7 ms).
-__global__ void __launch_bounds__(BLOCK) k_extract_count(
-    const int64_t *__restrict__ slot_keys, const double *__restrict__ slot_sums,
-    uint64_t cap, uint64_t chunk, uint64_t *__restrict__ block_counts) {
-  uint64_t lo = (uint64_t)blockIdx.x * chunk;
-  uint64_t hi = qk_min_u64(cap, lo + chunk);
-  uint32_t cnt = 0;
-  for (uint64_t st = lo + threadIdx.x; st < hi; st += BLOCK)
-    cnt += (slot_keys[st] != QK_JOIN_EMPTY && slot_sums[st] != 0.0) ? 1u : 0u;
-  uint64_t t = block_sum(cnt);
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = t;
-}
-
-__global__ void __launch_bounds__(BLOCK) k_extract_scatter(
-    const int64_t *__restrict__ slot_keys, const int32_t *__restrict__ slot_head,
-    const double *__restrict__ slot_sums, uint64_t cap, uint64_t chunk,
-    const uint64_t *__restrict__ block_offsets, int64_t *__restrict__ out_keys,
-    int32_t *__restrict__ out_row, double *__restrict__ out_sums,
-    uint64_t out_cap) {
-  uint64_t lo = (uint64_t)blockIdx.x * chunk;
-  uint64_t hi = qk_min_u64(cap, lo + chunk);
-  __shared__ uint64_t base;
-  __shared__ uint32_t wave_tot[BLOCK / WAVE];
-  if (threadIdx.x == 0) base = block_offsets[blockIdx.x];
-  __syncthreads();
-  int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  for (uint64_t s0 = lo; s0 < hi; s0 += BLOCK) {
-    uint64_t st = s0 + threadIdx.x;
-    bool live = st < hi && slot_keys[st] != QK_JOIN_EMPTY &&
-                slot_sums[st] != 0.0;
-    uint64_t mask = __ballot(live);
-    uint32_t rank = __popcll(mask & ((1ULL << lane) - 1));
-    if (lane == 0) wave_tot[wid] = __popcll(mask);
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (int w = 0; w < wid; w++) wbase += wave_tot[w];
-    if (live) {
-      uint64_t pos = base + wbase + rank;
-      if (pos < out_cap) {
-        out_keys[pos] = slot_keys[st];
-        out_row[pos] = slot_head[st];
-        out_sums[pos] = slot_sums[st];
-      }
-    }
-    uint32_t btot = 0;
-    for (int w = 0; w < BLOCK / WAVE; w++) btot += wave_tot[w];
-    __syncthreads();
-    if (threadIdx.x == 0) base += btot;
-    __syncthreads();
+struct Q3LivePred {
+  const int64_t *__restrict__ slot_keys;
+  const double *__restrict__ slot_sums;
+  __device__ bool operator()(uint64_t st) const {
+    return slot_keys[st] != QK_JOIN_EMPTY && slot_sums[st] != 0.0;
   }
-}
+};
+struct Q3Emit {
+  const int64_t *__restrict__ slot_keys;
+  const int32_t *__restrict__ slot_head;
+  const double *__restrict__ slot_sums;
+  int64_t *__restrict__ out_keys;
+  int32_t *__restrict__ out_row;
+  double *__restrict__ out_sums;
+  uint64_t out_cap;
+  __device__ void operator()(uint64_t st, uint64_t pos) const {
+    if (pos < out_cap) {
+      out_keys[pos] = slot_keys[st];
+      out_row[pos] = slot_head[st];
+      out_sums[pos] = slot_sums[st];
+    }
+  }
+};
 
 extern "C" int qk_q3_extract(void *stream, const int64_t *slot_keys,
                              const int32_t *slot_head,
@@ -1638,23 +1602,10 @@ extern "C" int qk_q3_extract(void *stream, const int64_t *slot_keys,
                              int64_t *out_keys, int32_t *out_row,
                              double *out_sums, uint64_t out_cap,
                              uint64_t *cursor) {
-  uint64_t chunk = (cap + MAX_BLOCKS - 1) / MAX_BLOCKS;
-  chunk = ((chunk + BLOCK - 1) / BLOCK) * BLOCK;
-  uint32_t blocks = (uint32_t)((cap + chunk - 1) / chunk);
-  static __thread uint64_t *scratch = nullptr;
-  if (!scratch) QK_TRY("qk_q3_extract", hipMalloc(&scratch,
-                       (MAX_BLOCKS + 1) * sizeof(uint64_t)));
-  hipLaunchKernelGGL(k_extract_count, dim3(blocks), dim3(BLOCK), 0,
-                     (hipStream_t)stream, slot_keys, slot_sums, cap, chunk,
-                     scratch);
-  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1), 0, (hipStream_t)stream,
-                     (uint64_t)blocks, scratch, cursor);
-  hipLaunchKernelGGL(k_extract_scatter, dim3(blocks), dim3(BLOCK), 0,
-                     (hipStream_t)stream, slot_keys, slot_head, slot_sums,
-                     cap, chunk, scratch, out_keys, out_row, out_sums,
-                     out_cap);
-  QK_TRY("qk_q3_extract", hipGetLastError());
-  return 0;
+  return qk_compact("qk_q3_extract", stream, 0, cap, cursor,
+                    Q3LivePred{slot_keys, slot_sums},
+                    Q3Emit{slot_keys, slot_head, slot_sums, out_keys, out_row,
+                           out_sums, out_cap});
 }
 
 // ---- fused Q5 path -----------------------------------------------------
@@ -2120,36 +2071,45 @@ extern "C" int qk_fill_f64(void *stream, double *dst, double v, uint64_t n) {
   return 0;
 }
 
+// Wave-aggregated claim on a shared cursor: the first lane of `mask` (not
+// 0) adds the wave's count with ONE atomicAdd, every lane of `mask` gets
+// its own position in the claimed range. Called by the whole wave.
+template <typename C>
+__device__ inline C wave_claim(C *cursor, uint64_t mask) {
+  int lane = (int)(threadIdx.x & (WAVE - 1));
+  int src = __ffsll((unsigned long long)mask) - 1;
+  C base = 0;
+  if (lane == src) base = atomicAdd(cursor, (C)__popcll(mask));
+  base = __shfl(base, src);
+  return base + (C)__popcll(mask & ((1ULL << lane) - 1));
+}
+
+// Compacts the occupied slots; with HAVING_GT (HAVING clauses) only the
+// groups with sums[col] > threshold — Q18 qualifies a handful of its
+// ~n_orders groups, so the d2h stays tiny instead of GBs. Reads
+// INTERLEAVED slot records, writes COLUMN-MAJOR outputs (consumers index
+// out_sums[c * out_cap + pos]).
+template <bool HAVING_GT>
 __global__ void __launch_bounds__(BLOCK) k_groupby_extract(
     const int64_t *__restrict__ table, int rstride, int nvals, uint64_t cap,
-    int64_t *__restrict__ out_keys, double *__restrict__ out_sums,
-    uint64_t out_cap, uint64_t *__restrict__ cursor) {
-  // wave-aggregated output cursor (one atomicAdd per wave per step);
-  // reads INTERLEAVED slot records, writes COLUMN-MAJOR outputs
-  // (consumers index out_sums[c * out_cap + pos])
+    int col, double threshold, int64_t *__restrict__ out_keys,
+    double *__restrict__ out_sums, uint64_t out_cap,
+    uint64_t *__restrict__ cursor) {
   uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  int lane = (int)(threadIdx.x & (WAVE - 1));
   for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < cap;
        s += stride) {
     const int64_t *rec = table + s * (uint64_t)rstride;
     int64_t key = rec[0];
+    const double *v = (const double *)(rec + 1);
     bool has = key != QK_JOIN_EMPTY;
+    if constexpr (HAVING_GT) has = has && v[col] > threshold;
     uint64_t mask = __ballot(has);
     if (!mask) continue;
-    int src = __ffsll((unsigned long long)mask) - 1;
-    unsigned long long base = 0;
-    if (lane == src)
-      base = atomicAdd((unsigned long long *)cursor,
-                       (unsigned long long)__popcll(mask));
-    base = __shfl(base, src);
-    if (has) {
-      uint64_t pos = base + __popcll(mask & ((1ULL << lane) - 1));
-      if (pos < out_cap) {
-        out_keys[pos] = key;
-        const double *v = (const double *)(rec + 1);
-        for (int c = 0; c < nvals; c++)
-          out_sums[(uint64_t)c * out_cap + pos] = v[c];
-      }
+    uint64_t pos = wave_claim((unsigned long long *)cursor, mask);
+    if (has && pos < out_cap) {
+      out_keys[pos] = key;
+      for (int c = 0; c < nvals; c++)
+        out_sums[(uint64_t)c * out_cap + pos] = v[c];
     }
   }
 }
@@ -2157,56 +2117,19 @@ extern "C" int qk_groupby_extract(void *stream, const int64_t *table,
                                   int rstride, int nvals, uint64_t cap,
                                   int64_t *out_keys, double *out_sums,
                                   uint64_t out_cap, uint64_t *cursor) {
-  uint32_t blocks = qk_grid(cap);
-  hipLaunchKernelGGL(k_groupby_extract, dim3(blocks), dim3(BLOCK), 0,
-                     (hipStream_t)stream, table, rstride, nvals, cap,
-                     out_keys, out_sums, out_cap, cursor);
+  hipLaunchKernelGGL(k_groupby_extract<false>, dim3(qk_grid(cap)),
+                     dim3(BLOCK), 0, (hipStream_t)stream, table, rstride,
+                     nvals, cap, 0, 0.0, out_keys, out_sums, out_cap, cursor);
   QK_TRY("qk_groupby_extract", hipGetLastError());
   return 0;
-}
-
-// Thresholded extract (HAVING clauses): only groups with
-// sums[col] > threshold are compacted — Q18 qualifies a handful of its
-// ~n_orders groups, so the d2h stays tiny instead of GBs.
-__global__ void __launch_bounds__(BLOCK) k_groupby_extract_gt(
-    const int64_t *__restrict__ table, int rstride, int nvals, uint64_t cap,
-    int col, double threshold, int64_t *__restrict__ out_keys,
-    double *__restrict__ out_sums, uint64_t out_cap,
-    uint64_t *__restrict__ cursor) {
-  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  int lane = (int)(threadIdx.x & (WAVE - 1));
-  for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < cap;
-       s += stride) {
-    const int64_t *rec = table + s * (uint64_t)rstride;
-    int64_t key = rec[0];
-    const double *v = (const double *)(rec + 1);
-    bool has = key != QK_JOIN_EMPTY && v[col] > threshold;
-    uint64_t mask = __ballot(has);
-    if (!mask) continue;
-    int src = __ffsll((unsigned long long)mask) - 1;
-    unsigned long long base = 0;
-    if (lane == src)
-      base = atomicAdd((unsigned long long *)cursor,
-                       (unsigned long long)__popcll(mask));
-    base = __shfl(base, src);
-    if (has) {
-      uint64_t pos = base + __popcll(mask & ((1ULL << lane) - 1));
-      if (pos < out_cap) {
-        out_keys[pos] = key;
-        for (int c = 0; c < nvals; c++)
-          out_sums[(uint64_t)c * out_cap + pos] = v[c];
-      }
-    }
-  }
 }
 extern "C" int qk_groupby_extract_gt(void *stream, const int64_t *table,
                                      int rstride, int nvals, uint64_t cap,
                                      int col, double threshold,
                                      int64_t *out_keys, double *out_sums,
                                      uint64_t out_cap, uint64_t *cursor) {
-  uint32_t blocks = qk_grid(cap);
-  hipLaunchKernelGGL(k_groupby_extract_gt, dim3(blocks), dim3(BLOCK), 0,
-                     (hipStream_t)stream, table, rstride, nvals, cap, col,
+  hipLaunchKernelGGL(k_groupby_extract<true>, dim3(qk_grid(cap)), dim3(BLOCK),
+                     0, (hipStream_t)stream, table, rstride, nvals, cap, col,
                      threshold, out_keys, out_sums, out_cap, cursor);
   QK_TRY("qk_groupby_extract_gt", hipGetLastError());
   return 0;
@@ -2822,10 +2745,7 @@ __global__ void __launch_bounds__(BLOCK) k_valid_expand(
     const uint64_t *__restrict__ block_offsets, T *__restrict__ out) {
   uint64_t lo = (uint64_t)blockIdx.x * chunk;
   uint64_t hi = qk_min_u64(n, lo + chunk);
-  __shared__ uint64_t base;
-  __shared__ uint32_t wave_tot[BLOCK / WAVE];
-  if (threadIdx.x == 0) base = block_offsets[blockIdx.x];
-  __syncthreads();
+  uint64_t base = block_offsets[blockIdx.x];
   int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
   for (uint64_t r0 = lo; r0 < hi; r0 += BLOCK) {
     uint64_t r = r0 + threadIdx.x;
@@ -2833,18 +2753,8 @@ __global__ void __launch_bounds__(BLOCK) k_valid_expand(
     // bits >= n are 0, so a word that straddles n needs no mask; a wave
     // wholly past hi reads nothing
     uint64_t mask = wave_row < hi ? valid[wave_row >> 6] : 0;
-    bool set = (mask >> lane) & 1;
-    uint32_t rank = __popcll(mask & ((1ULL << lane) - 1));
-    if (lane == 0) wave_tot[wid] = __popcll(mask);
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (int w = 0; w < wid; w++) wbase += wave_tot[w];
-    if (r < hi) out[r] = set ? dense[base + wbase + rank] : (T)0;
-    uint32_t btot = 0;
-    for (int w = 0; w < BLOCK / WAVE; w++) btot += wave_tot[w];
-    __syncthreads();
-    if (threadIdx.x == 0) base += btot;
-    __syncthreads();
+    uint64_t pos = compact_step(mask, base);
+    if (r < hi) out[r] = ((mask >> lane) & 1) ? dense[pos] : (T)0;
   }
 }
 extern "C" int qk_valid_expand(void *stream, uint64_t n,
@@ -2854,9 +2764,8 @@ extern "C" int qk_valid_expand(void *stream, uint64_t n,
   if (elem_size != 4 && elem_size != 8)
     return qk_fail("qk_valid_expand.elem_size", hipErrorInvalidValue);
   if (!n) return 0;
-  uint64_t rows_per_block = (n + MAX_BLOCKS - 1) / MAX_BLOCKS;
-  rows_per_block = ((rows_per_block + BLOCK - 1) / BLOCK) * BLOCK;
-  uint32_t blocks = (uint32_t)((n + rows_per_block - 1) / rows_per_block);
+  uint64_t rows_per_block;
+  uint32_t blocks = qk_compact_blocks(n, &rows_per_block);
   static __thread uint64_t *scratch = nullptr;  // block counts + total
   if (!scratch)
     QK_TRY("qk_valid_expand",
@@ -3194,14 +3103,13 @@ __global__ void __launch_bounds__(BLOCK) k_keydict_claim(
 }
 
 // (b) finalise: the claiming row of each new slot takes a dense code (one
-// atomicAdd per wave, as k_groupby_extract), copies its K words into the
+// atomicAdd per wave, wave_claim), copies its K words into the
 // key store and rewrites the slot as tag | code
 __global__ void __launch_bounds__(BLOCK) k_keydict_finalise(
     uint64_t n, int nkeys, const int64_t *const *__restrict__ cols,
     uint64_t *slots, int64_t *__restrict__ store, uint64_t code_cap,
     const uint64_t *__restrict__ row_slot, uint32_t *counter, uint32_t *err) {
   uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  int lane = (int)(threadIdx.x & (WAVE - 1));
   // whole waves stay in the loop (b0 is wave-uniform) for the ballot
   for (uint64_t b0 = (uint64_t)blockIdx.x * blockDim.x; b0 < n; b0 += stride) {
     uint64_t i = b0 + threadIdx.x;
@@ -3210,12 +3118,8 @@ __global__ void __launch_bounds__(BLOCK) k_keydict_finalise(
     bool claimant = (w & QK_KD_PENDING) && (w & 0xFFFFFFFFULL) == (uint32_t)i;
     uint64_t mask = __ballot(claimant);
     if (!mask) continue;
-    int src = __ffsll((unsigned long long)mask) - 1;
-    uint32_t base = 0;
-    if (lane == src) base = atomicAdd(counter, (uint32_t)__popcll(mask));
-    base = __shfl(base, src);
+    uint64_t code = wave_claim(counter, mask);
     if (claimant) {
-      uint64_t code = base + (uint32_t)__popcll(mask & ((1ULL << lane) - 1));
       if (code < code_cap && code < QK_KD_NOCODE) {
         for (int k = 0; k < nkeys; k++)
           store[(uint64_t)k * code_cap + code] = cols[k][i];
@@ -3429,62 +3333,21 @@ extern "C" int qk_groupby_dense_init(void *stream, double *acc, uint64_t first,
   return 0;
 }
 
+// HAS_VALID: the same accumulate over value columns with SQL NULLs
+// (DuckDB's SUM / MIN / MAX skip them, and an aggregate that met no value
+// is NULL, sql_executors.py:556-599). valid[c] is column c's validity
+// bitmap or 0 for a column without nulls, tested before anything of it is
+// read. As in k_key_null_words a wave covers 64 consecutive, 64-aligned
+// rows, so a column's validity word is one load of the same address for
+// the whole wave and each lane tests its own bit; only lanes with i < n
+// run, so the bits of the last word past n reach nothing, and the value
+// under a 0 bit is never loaded. seen[code] collects one bit per column
+// that has received a value. The plain read in front of the atomicOr can
+// only be stale towards fewer bits: it costs a redundant atomic, never a
+// lost one, and once a group's bits stand its rows pay one mostly-cached
+// load. Without HAS_VALID, `valid` and `seen` are null and never touched.
+template <bool HAS_VALID>
 __global__ void __launch_bounds__(BLOCK) k_groupby_dense_acc(
-    uint64_t n, const uint32_t *__restrict__ codes, uint32_t ncodes,
-    const double *const *__restrict__ vals,
-    const int32_t *__restrict__ agg_ops, int nvals, int rstride, double *acc,
-    uint32_t *err) {
-  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride) {
-    uint32_t code = codes[i];
-    if (code >= ncodes) {  // never written past the records the host sized
-      atomicOr(err, 4u);
-      continue;
-    }
-    double *rec = acc + (uint64_t)code * (uint64_t)rstride;
-    for (int c = 0; c < nvals; c++) {
-      double v = vals[c][i];
-      int op = agg_ops ? agg_ops[c] : 0;
-      if (op == 1)
-        atomic_min_f64(&rec[c], v);
-      else if (op == 2)
-        atomic_max_f64(&rec[c], v);
-      else
-        atomicAdd(&rec[c], v);
-    }
-  }
-}
-extern "C" int qk_groupby_dense_acc(void *stream, uint64_t n,
-                                    const uint32_t *codes, uint32_t ncodes,
-                                    const void *vals_dev,
-                                    const int32_t *agg_ops_dev, int nvals,
-                                    int rstride, double *acc,
-                                    uint32_t *err_dev) {
-  if (!n || !nvals) return 0;
-  if (nvals < 0 || rstride < nvals || !qk_pow2((uint64_t)rstride))
-    return qk_fail("qk_groupby_dense_acc.rstride", hipErrorInvalidValue);
-  hipLaunchKernelGGL(k_groupby_dense_acc, dim3(qk_grid(n)), dim3(BLOCK), 0,
-                     (hipStream_t)stream, n, codes, ncodes,
-                     (const double *const *)vals_dev, agg_ops_dev, nvals,
-                     rstride, acc, err_dev);
-  QK_TRY("qk_groupby_dense_acc", hipGetLastError());
-  return 0;
-}
-
-// The same accumulate over value columns with SQL NULLs (DuckDB's SUM / MIN
-// / MAX skip them, and an aggregate that met no value is NULL,
-// sql_executors.py:556-599). valid[c] is column c's validity bitmap or 0
-// for a column without nulls, tested before anything of it is read. As in
-// k_key_null_words a wave covers 64 consecutive, 64-aligned rows, so a
-// column's validity word is one load of the same address for the whole
-// wave and each lane tests its own bit; only lanes with i < n run, so the
-// bits of the last word past n reach nothing, and the value under a 0 bit
-// is never loaded. seen[code] collects one bit per column that has
-// received a value. The plain read in front of the atomicOr can only be
-// stale towards fewer bits: it costs a redundant atomic, never a lost one,
-// and once a group's bits stand its rows pay one mostly-cached load.
-__global__ void __launch_bounds__(BLOCK) k_groupby_dense_acc_valid(
     uint64_t n, const uint32_t *__restrict__ codes, uint32_t ncodes,
     const double *const *__restrict__ vals,
     const uint64_t *const *__restrict__ valid,
@@ -3502,8 +3365,11 @@ __global__ void __launch_bounds__(BLOCK) k_groupby_dense_acc_valid(
     double *rec = acc + (uint64_t)code * (uint64_t)rstride;
     uint64_t m = 0;
     for (int c = 0; c < nvals; c++) {
-      const uint64_t *vp = valid[c];
-      if (vp && !((vp[i >> 6] >> lane) & 1)) continue;
+      if constexpr (HAS_VALID) {
+        const uint64_t *vp = valid[c];
+        if (vp && !((vp[i >> 6] >> lane) & 1)) continue;
+        m |= 1ULL << c;
+      }
       double v = vals[c][i];
       int op = agg_ops ? agg_ops[c] : 0;
       if (op == 1)
@@ -3512,11 +3378,28 @@ __global__ void __launch_bounds__(BLOCK) k_groupby_dense_acc_valid(
         atomic_max_f64(&rec[c], v);
       else
         atomicAdd(&rec[c], v);
-      m |= 1ULL << c;
     }
-    if (m && (seen[code] & m) != m)
-      atomicOr((unsigned long long *)&seen[code], (unsigned long long)m);
+    if constexpr (HAS_VALID)
+      if (m && (seen[code] & m) != m)
+        atomicOr((unsigned long long *)&seen[code], (unsigned long long)m);
   }
+}
+extern "C" int qk_groupby_dense_acc(void *stream, uint64_t n,
+                                    const uint32_t *codes, uint32_t ncodes,
+                                    const void *vals_dev,
+                                    const int32_t *agg_ops_dev, int nvals,
+                                    int rstride, double *acc,
+                                    uint32_t *err_dev) {
+  if (!n || !nvals) return 0;
+  if (nvals < 0 || rstride < nvals || !qk_pow2((uint64_t)rstride))
+    return qk_fail("qk_groupby_dense_acc.rstride", hipErrorInvalidValue);
+  hipLaunchKernelGGL(k_groupby_dense_acc<false>, dim3(qk_grid(n)),
+                     dim3(BLOCK), 0, (hipStream_t)stream, n, codes, ncodes,
+                     (const double *const *)vals_dev,
+                     (const uint64_t *const *)nullptr, agg_ops_dev, nvals,
+                     rstride, acc, (uint64_t *)nullptr, err_dev);
+  QK_TRY("qk_groupby_dense_acc", hipGetLastError());
+  return 0;
 }
 extern "C" int qk_groupby_dense_acc_valid(void *stream, uint64_t n,
                                           const uint32_t *codes,
@@ -3532,7 +3415,7 @@ extern "C" int qk_groupby_dense_acc_valid(void *stream, uint64_t n,
     return qk_fail("qk_groupby_dense_acc_valid.rstride", hipErrorInvalidValue);
   if (!codes || !vals_dev || !valid_ptrs_dev || !acc || !seen || !err_dev)
     return qk_fail("qk_groupby_dense_acc_valid.args", hipErrorInvalidValue);
-  hipLaunchKernelGGL(k_groupby_dense_acc_valid, dim3(qk_grid(n)), dim3(BLOCK),
+  hipLaunchKernelGGL(k_groupby_dense_acc<true>, dim3(qk_grid(n)), dim3(BLOCK),
                      0, (hipStream_t)stream, n, codes, ncodes,
                      (const double *const *)vals_dev,
                      (const uint64_t *const *)valid_ptrs_dev, agg_ops_dev,
@@ -4545,70 +4428,21 @@ extern "C" int qk_range_part_ids(void *stream, uint64_t n,
 // newline index (same count/scan/scatter shape as the filter), then a
 // thread-per-row typed field parser.
 
-__global__ void __launch_bounds__(BLOCK) k_csv_nl_count(
-    uint64_t lo0, uint64_t n, const uint8_t *__restrict__ b, uint64_t chunk,
-    uint64_t *__restrict__ block_counts) {
-  uint64_t lo = lo0 + (uint64_t)blockIdx.x * chunk;
-  uint64_t hi = qk_min_u64(n, lo + chunk);
-  uint32_t cnt = 0;
-  for (uint64_t r = lo + threadIdx.x; r < hi; r += BLOCK)
-    cnt += b[r] == '\n' ? 1u : 0u;
-  uint64_t s = block_sum(cnt);
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = s;
-}
-
-__global__ void __launch_bounds__(BLOCK) k_csv_nl_scatter(
-    uint64_t lo0, uint64_t n, const uint8_t *__restrict__ b, uint64_t chunk,
-    const uint64_t *__restrict__ block_offsets, uint64_t *__restrict__ out) {
-  uint64_t lo = lo0 + (uint64_t)blockIdx.x * chunk;
-  uint64_t hi = qk_min_u64(n, lo + chunk);
-  __shared__ uint64_t base;
-  __shared__ uint32_t wave_tot[BLOCK / WAVE];
-  if (threadIdx.x == 0) base = block_offsets[blockIdx.x];
-  __syncthreads();
-  int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  for (uint64_t r0 = lo; r0 < hi; r0 += BLOCK) {
-    uint64_t r = r0 + threadIdx.x;
-    bool pass = r < hi && b[r] == '\n';
-    uint64_t mask = __ballot(pass);
-    uint32_t rank = __popcll(mask & ((1ULL << lane) - 1));
-    uint32_t wtot = __popcll(mask);
-    if (lane == 0) wave_tot[wid] = wtot;
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (int w = 0; w < wid; w++) wbase += wave_tot[w];
-    if (pass) out[base + wbase + rank] = r;
-    uint32_t btot = 0;
-    for (int w = 0; w < BLOCK / WAVE; w++) btot += wave_tot[w];
-    __syncthreads();
-    if (threadIdx.x == 0) base += btot;
-    __syncthreads();
-  }
-}
+struct NewlinePred {
+  const uint8_t *__restrict__ b;
+  __device__ bool operator()(uint64_t r) const { return b[r] == '\n'; }
+};
+struct EmitPosU64 {
+  uint64_t *__restrict__ out;
+  __device__ void operator()(uint64_t r, uint64_t pos) const { out[pos] = r; }
+};
 
 extern "C" int qk_csv_newlines(void *stream, uint64_t data_start, uint64_t n,
                                const uint8_t *bytes, uint64_t *out_pos,
                                uint64_t *out_count_dev) {
   if (n <= data_start) return 0;
-  uint64_t span = n - data_start;
-  uint64_t chunk = (span + MAX_BLOCKS - 1) / MAX_BLOCKS;
-  chunk = ((chunk + BLOCK - 1) / BLOCK) * BLOCK;
-  uint32_t blocks = (uint32_t)((span + chunk - 1) / chunk);
-  static __thread uint64_t *scratch = nullptr;
-  if (!scratch)
-    QK_TRY("qk_csv_newlines",
-           hipMalloc(&scratch, (MAX_BLOCKS + 1) * sizeof(uint64_t)));
-  hipLaunchKernelGGL(k_csv_nl_count, dim3(blocks), dim3(BLOCK), 0,
-                     (hipStream_t)stream, data_start, n, bytes, chunk,
-                     scratch);
-  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1), 0,
-                     (hipStream_t)stream, (uint64_t)blocks, scratch,
-                     out_count_dev);
-  hipLaunchKernelGGL(k_csv_nl_scatter, dim3(blocks), dim3(BLOCK), 0,
-                     (hipStream_t)stream, data_start, n, bytes, chunk,
-                     scratch, out_pos);
-  QK_TRY("qk_csv_newlines", hipGetLastError());
-  return 0;
+  return qk_compact("qk_csv_newlines", stream, data_start, n, out_count_dev,
+                    NewlinePred{bytes}, EmitPosU64{out_pos});
 }
 
 // Quote-aware newline indexing (RFC-4180): a '\n' ends a row only when

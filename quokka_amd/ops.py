@@ -166,16 +166,13 @@ class JoinTable:
                 % (self.n_build, n, min(self.chain_cap, self.cap // 2)))
         sh = self.stream.handle if self.stream else None
         bitmap, owned = _key_bitmap(keys_col, valid, n)
+        table = (c_u32(self.n_build), self.slot_keys.ptr, self.slot_head.ptr,
+                 self.chain_next.ptr, c_u64(self.cap))
         if bitmap is None:
-            shim.call("qk_join_build", sh, c_u64(n), keys_col.ptr,
-                      c_u32(self.n_build), self.slot_keys.ptr,
-                      self.slot_head.ptr, self.chain_next.ptr,
-                      c_u64(self.cap))
+            shim.call("qk_join_build", sh, c_u64(n), keys_col.ptr, *table)
         else:
             shim.call("qk_join_build_valid", sh, c_u64(n), keys_col.ptr,
-                      bitmap.ptr, c_u32(self.n_build), self.slot_keys.ptr,
-                      self.slot_head.ptr, self.chain_next.ptr,
-                      c_u64(self.cap))
+                      bitmap.ptr, *table)
             if owned:
                 shim.call("qk_stream_sync", sh)
                 bitmap.free()
@@ -194,18 +191,13 @@ class JoinTable:
             probe_idx = DevColumn(np.uint32, out_cap)
             build_idx = DevColumn(np.uint32, out_cap) if mode == 0 else None
             cur = _count_buf()
-            if bitmap is None:
-                shim.call("qk_join_probe", sh, c_u64(n), keys_col.ptr,
-                          self.slot_keys.ptr, self.slot_head.ptr,
-                          self.chain_next.ptr, c_u64(self.cap), mode,
-                          probe_idx.ptr, build_idx.ptr if build_idx else None,
-                          c_u64(out_cap), cur.ptr)
-            else:
-                shim.call("qk_join_probe_valid", sh, c_u64(n), keys_col.ptr,
-                          bitmap.ptr, self.slot_keys.ptr, self.slot_head.ptr,
-                          self.chain_next.ptr, c_u64(self.cap), mode,
-                          probe_idx.ptr, build_idx.ptr if build_idx else None,
-                          c_u64(out_cap), cur.ptr)
+            name, keys = ("qk_join_probe", (keys_col.ptr,)) if bitmap is None \
+                else ("qk_join_probe_valid", (keys_col.ptr, bitmap.ptr))
+            shim.call(name, sh, c_u64(n), *keys, self.slot_keys.ptr,
+                      self.slot_head.ptr, self.chain_next.ptr,
+                      c_u64(self.cap), mode, probe_idx.ptr,
+                      build_idx.ptr if build_idx else None, c_u64(out_cap),
+                      cur.ptr)
             if self.stream:
                 self.stream.sync()
             total = _read_u64(cur)
@@ -325,18 +317,7 @@ class GroupByI64:
 
     def extract(self):
         """-> (keys np.int64[K], sums np.float64[nvals, K]); unordered."""
-        sh = self.stream.handle if self.stream else None
-        out_cap = self.cap
-        out_keys = DevColumn(np.int64, out_cap)
-        out_sums = DevColumn(np.float64, out_cap * self.nvals)
-        cur = _count_buf()
-        shim.call("qk_groupby_extract", sh, self.table.ptr,
-                  self.rstride, self.nvals, c_u64(self.cap),
-                  out_keys.ptr, out_sums.ptr, c_u64(out_cap), cur.ptr)
-        if self.stream:
-            self.stream.sync()
-        k = _read_u64(cur)
-        cur.free()
+        out_keys, out_sums, k, out_cap = self.extract_device()
         keys = out_keys.to_numpy(k)
         # d2h only the K occupied entries of each value column (the
         # compaction writes column c at [c*out_cap, c*out_cap + K) —
