@@ -197,7 +197,8 @@ int qk_gather_u8(void *stream, uint64_t n_idx, const uint32_t *idx,
 /* ---- hash join build / probe (i64 keys) ------------------------------- *
  * Replaces BuildProbeJoinExecutor (sql_executors.py:325-377): build side =
  * stream 1 (vstacked state), probe = stream 0, how in {inner,semi,anti}
- * (left via inner + host fill). Open-addressing table, linear probing,
+ * (left via inner + host fill, or on the device in probe mode 3).
+ * Open-addressing table, linear probing,
  * capacity a power of two >= 2x build rows. Duplicate build keys chain
  * through chain_next. slot_keys must be pre-filled with QK_JOIN_EMPTY
  * (qk_fill_i64), slot_head with -1 bytes (qk_dmemset 0xff).
@@ -215,9 +216,15 @@ int qk_join_build(void *stream, uint64_t n_build, const int64_t *keys,
                   uint32_t build_row_offset, int64_t *slot_keys,
                   int32_t *slot_head, int32_t *chain_next, uint64_t capacity);
 /* mode: 0 = inner (emit probe_idx,build_idx pairs), 1 = semi (probe_idx
- * only), 2 = anti (probe_idx only). out_cursor_dev (u64, zeroed) returns the
- * TOTAL match count even when it exceeds out_capacity (no silent
- * truncation: caller re-runs with larger buffers when cursor > capacity). */
+ * only), 2 = anti (probe_idx only), 3 = left: inner, plus one pair
+ * (probe_idx, QK_NO_ROW) for every probe row without a match, so a row
+ * with d matches appears max(1, d) times. out_cursor_dev (u64, zeroed)
+ * returns the TOTAL pair count even when it exceeds out_capacity (no silent
+ * truncation: caller re-runs with larger buffers when cursor > capacity).
+ * QK_NO_ROW is the build index of "no build row". Build rows are int32
+ * chain indices, so no real row reaches it. Modes 0 and 3 need
+ * out_build_idx. */
+#define QK_NO_ROW 0xFFFFFFFFu
 int qk_join_probe(void *stream, uint64_t n_probe, const int64_t *keys,
                   const int64_t *slot_keys, const int32_t *slot_head,
                   const int32_t *chain_next, uint64_t capacity, int mode,
@@ -233,7 +240,8 @@ int qk_join_probe(void *stream, uint64_t n_probe, const int64_t *keys,
  * number build_row_offset + i, so the caller still advances its build
  * count by n_build and build indices keep addressing the payload columns.
  * Probe: a null row is a miss decided without a walk: nothing in mode 0
- * and 1, emitted in mode 2. Everything else as qk_join_build /
+ * and 1, emitted in mode 2, emitted once with QK_NO_ROW in mode 3.
+ * Everything else as qk_join_build /
  * qk_join_probe, which remain the entry points for columns without a
  * bitmap. */
 int qk_join_build_valid(void *stream, uint64_t n_build, const int64_t *keys,
@@ -578,6 +586,34 @@ int qk_valid_to_u8(void *stream, uint64_t n, const uint64_t *valid_dev,
 int qk_valid_gather(void *stream, uint64_t n_idx, const uint32_t *idx,
                     const uint64_t *valid_dev, uint64_t *out_valid_dev,
                     uint64_t *out_null_count_dev);
+/* Optional gather, value and validity in one pass over idx (the emit of a
+ * join whose payload columns hold NULLs, and of the left join, whose
+ * unmatched rows have no build row). Row i is valid iff idx[i] != QK_NO_ROW
+ * and (src_valid_dev == NULL, meaning every source row is valid, or bit
+ * idx[i] of src_valid_dev is set). A valid row writes dst[i] = src[idx[i]];
+ * an invalid row writes dst[i] = 0 and does not read src, so null slots
+ * hold 0 and the value under a source null is never used. out_valid_dev
+ * gets ceil(n_idx / 64) whole words, bits at an index >= n_idx 0; the
+ * caller zeroes the slack word behind them. The null count is ADDED to
+ * *out_null_count_dev (caller zeroes it). n_idx == 0 launches nothing.
+ * PRECONDITION: every index other than QK_NO_ROW is below the source
+ * length (rows of src, bits of src_valid_dev); the kernel does not check. */
+int qk_take_opt_i64(void *stream, uint64_t n_idx, const uint32_t *idx,
+                    const int64_t *src, const uint64_t *src_valid_dev,
+                    int64_t *dst, uint64_t *out_valid_dev,
+                    uint64_t *out_null_count_dev);
+int qk_take_opt_f64(void *stream, uint64_t n_idx, const uint32_t *idx,
+                    const double *src, const uint64_t *src_valid_dev,
+                    double *dst, uint64_t *out_valid_dev,
+                    uint64_t *out_null_count_dev);
+int qk_take_opt_i32(void *stream, uint64_t n_idx, const uint32_t *idx,
+                    const int32_t *src, const uint64_t *src_valid_dev,
+                    int32_t *dst, uint64_t *out_valid_dev,
+                    uint64_t *out_null_count_dev);
+int qk_take_opt_u8(void *stream, uint64_t n_idx, const uint32_t *idx,
+                   const uint8_t *src, const uint64_t *src_valid_dev,
+                   uint8_t *dst, uint64_t *out_valid_dev,
+                   uint64_t *out_null_count_dev);
 /* ---- device string dictionary ---------------------------------------- *
  * General variable-width string keys for join/group-by (the reference
  * joins/groups on arbitrary key types via polars, sql_executors.py:

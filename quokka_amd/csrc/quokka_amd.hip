@@ -1154,7 +1154,8 @@ extern "C" int qk_join_build_valid(void *stream, uint64_t n,
 }
 
 // A null probe row is a miss without a walk: nothing for inner and semi,
-// emitted for anti.
+// emitted for anti. Mode 3 (left) is inner plus a miss rule: a miss, null
+// keys included, claims one position and pairs the row with QK_NO_ROW.
 template <bool HAS_VALID>
 __global__ void __launch_bounds__(BLOCK) k_join_probe(
     uint64_t n, const int64_t *__restrict__ keys,
@@ -1170,14 +1171,23 @@ __global__ void __launch_bounds__(BLOCK) k_join_probe(
     if constexpr (HAS_VALID) null_key = !qk_valid_bit(valid, i);
     int32_t head = null_key ? -1 : probe_unique(slot_keys, slot_head, cap,
                                                 keys[i], nullptr);
-    if (mode != 0) {  // semi emits hits, anti emits misses
+    if (mode != 0 && mode != 3) {  // semi emits hits, anti emits misses
       if ((head >= 0) == (mode == 1)) {
         uint64_t pos = atomicAdd((unsigned long long *)cursor, 1ULL);
         if (pos < out_cap) out_probe[pos] = (uint32_t)i;
       }
       continue;
     }
-    if (head < 0) continue;
+    if (head < 0) {
+      if (mode == 3) {  // left: the row once, with no build row
+        uint64_t pos = atomicAdd((unsigned long long *)cursor, 1ULL);
+        if (pos < out_cap) {
+          out_probe[pos] = (uint32_t)i;
+          out_build[pos] = QK_NO_ROW;
+        }
+      }
+      continue;
+    }
     // inner: count chain, claim a contiguous range, emit
     uint32_t cnt = 0;
     for (int32_t b = head; b >= 0; b = chain_next[b]) cnt++;
@@ -1198,6 +1208,8 @@ extern "C" int qk_join_probe(void *stream, uint64_t n, const int64_t *keys,
                              uint64_t out_cap, uint64_t *cursor) {
   if (!n) return 0;
   if (!qk_pow2(cap)) return qk_fail("qk_join_probe.cap_pow2", hipErrorInvalidValue);
+  if (mode == 3 && !out_build)
+    return qk_fail("qk_join_probe.args", hipErrorInvalidValue);
   hipLaunchKernelGGL(k_join_probe<false>, dim3(qk_grid(n)), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, keys, (const uint8_t *)nullptr,
                      slot_keys, slot_head, chain_next, cap, mode, out_probe,
@@ -1217,7 +1229,8 @@ extern "C" int qk_join_probe_valid(void *stream, uint64_t n,
   if (!n) return 0;
   if (!qk_pow2(cap))
     return qk_fail("qk_join_probe_valid.cap_pow2", hipErrorInvalidValue);
-  if (!valid_dev || mode < 0 || mode > 2 || (mode == 0 && !out_build))
+  if (!valid_dev || mode < 0 || mode > 3 ||
+      ((mode == 0 || mode == 3) && !out_build))
     return qk_fail("qk_join_probe_valid.args", hipErrorInvalidValue);
   hipLaunchKernelGGL(k_join_probe<true>, dim3(qk_grid(n)), dim3(BLOCK), 0,
                      (hipStream_t)stream, n, keys, (const uint8_t *)valid_dev,
@@ -2842,6 +2855,76 @@ extern "C" int qk_valid_gather(void *stream, uint64_t n_idx,
                      out_null_count_dev);
   QK_TRY("qk_valid_gather", hipGetLastError());
   return 0;
+}
+
+// Optional gather: value and validity of the rows idx[0..n_idx) selects in
+// one pass over idx. A row is valid when its index is not QK_NO_ROW (the
+// left join's "no build row") and, under HAS_VALID, the source's bit is
+// set; an invalid row gets 0 and src is not read for it. The validity word
+// is packed as in k_valid_gather above.
+template <typename T, bool HAS_VALID>
+__global__ void __launch_bounds__(BLOCK) k_take_opt(
+    uint64_t n, const uint32_t *__restrict__ idx, const T *__restrict__ src,
+    const uint8_t *__restrict__ src_valid, T *__restrict__ dst,
+    uint64_t *__restrict__ out_valid, uint64_t *__restrict__ null_count) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  uint32_t lane = threadIdx.x & (WAVE - 1);
+  uint32_t nulls = 0;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x - lane;
+       i0 < n; i0 += stride) {
+    uint64_t i = i0 + lane;
+    bool bit = false;
+    if (i < n) {
+      uint32_t r = idx[i];
+      bit = r != QK_NO_ROW;
+      if constexpr (HAS_VALID)
+        if (bit) bit = qk_valid_bit(src_valid, r);
+      dst[i] = bit ? src[r] : T(0);
+      nulls += bit ? 0u : 1u;
+    }
+    uint64_t m = __ballot(bit);
+    if (lane == 0) out_valid[i0 >> 6] = m;
+  }
+  block_add_count(nulls, null_count);
+}
+template <typename T>
+static int qk_take_opt_impl(const char *who, void *stream, uint64_t n,
+                            const uint32_t *idx, const T *src,
+                            const uint64_t *src_valid, T *dst,
+                            uint64_t *out_valid, uint64_t *null_count) {
+  if (!n) return 0;
+  if (!idx || !src || !dst || !out_valid || !null_count)
+    return qk_fail(who, hipErrorInvalidValue);
+  if (src_valid)
+    hipLaunchKernelGGL((k_take_opt<T, true>), dim3(qk_grid(n)), dim3(BLOCK), 0,
+                       (hipStream_t)stream, n, idx, src,
+                       (const uint8_t *)src_valid, dst, out_valid, null_count);
+  else
+    hipLaunchKernelGGL((k_take_opt<T, false>), dim3(qk_grid(n)), dim3(BLOCK),
+                       0, (hipStream_t)stream, n, idx, src,
+                       (const uint8_t *)nullptr, dst, out_valid, null_count);
+  QK_TRY(who, hipGetLastError());
+  return 0;
+}
+extern "C" int qk_take_opt_i64(void *s, uint64_t n, const uint32_t *i,
+                               const int64_t *src, const uint64_t *sv,
+                               int64_t *dst, uint64_t *ov, uint64_t *nc) {
+  return qk_take_opt_impl("qk_take_opt_i64", s, n, i, src, sv, dst, ov, nc);
+}
+extern "C" int qk_take_opt_f64(void *s, uint64_t n, const uint32_t *i,
+                               const double *src, const uint64_t *sv,
+                               double *dst, uint64_t *ov, uint64_t *nc) {
+  return qk_take_opt_impl("qk_take_opt_f64", s, n, i, src, sv, dst, ov, nc);
+}
+extern "C" int qk_take_opt_i32(void *s, uint64_t n, const uint32_t *i,
+                               const int32_t *src, const uint64_t *sv,
+                               int32_t *dst, uint64_t *ov, uint64_t *nc) {
+  return qk_take_opt_impl("qk_take_opt_i32", s, n, i, src, sv, dst, ov, nc);
+}
+extern "C" int qk_take_opt_u8(void *s, uint64_t n, const uint32_t *i,
+                              const uint8_t *src, const uint64_t *sv,
+                              uint8_t *dst, uint64_t *ov, uint64_t *nc) {
+  return qk_take_opt_impl("qk_take_opt_u8", s, n, i, src, sv, dst, ov, nc);
 }
 
 // ---- device string dictionary ------------------------------------------

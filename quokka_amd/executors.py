@@ -82,6 +82,55 @@ def _concat_col(parts):
     return pa.chunked_array(chunks)
 
 
+def _split_payload(name, col, staging):
+    """One numeric join payload column (null_payloads=True) -> (host values
+    in the device storage type, bool mask or None when it has no nulls).
+    bool is stored as uint8, date32 as int32, narrow ints as int64 and
+    float32 as float64 (all exact, cast back at emit); int64 stays int64.
+    Anything else raises TypeError: nothing is staged approximately."""
+    import pyarrow as pa
+    t = col.type
+    if not (pa.types.is_boolean(t) or pa.types.is_date32(t) or
+            pa.types.is_signed_integer(t) or pa.types.is_uint8(t) or
+            pa.types.is_uint32(t) or pa.types.is_float32(t) or
+            pa.types.is_float64(t)):
+        raise TypeError("join payload column %r: type %s unsupported with "
+                        "null_payloads=True (ints, date32, bool, floats and "
+                        "strings are)" % (name, t))
+    if not col.null_count:
+        return staging.column_to_numpy(col), None
+    filled, mask = staging.split_nulls(col)
+    return staging.column_to_numpy(filled), mask
+
+
+def _payload_device(ops, shim, values, mask):
+    """Staged payload -> DevColumn, or NullableColumn when it has nulls."""
+    if mask is None or mask.all():
+        return shim.DevColumn.from_numpy(values)
+    return ops.NullableColumn.from_numpy(values, mask)
+
+
+def _take_to_arrow(ops, src, idx, n_idx, arrow_type):
+    """src[idx] through the optional gather (NO_ROW and source nulls come
+    back NULL) as a host Arrow array of arrow_type; the cast from the
+    storage type keeps the validity buffer."""
+    from . import bridge
+    g = ops.take_optional(src, idx, n_idx)
+    arr = bridge.column_to_arrow(g)
+    g.free()
+    return arr if arr.type == arrow_type else arr.cast(arrow_type)
+
+
+def _take_strings(col, rows, no_row=None):
+    """Host Arrow take of a string column at device-produced row indices;
+    an index equal to no_row selects NULL."""
+    import pyarrow as pa
+    if isinstance(col, pa.ChunkedArray):
+        col = col.combine_chunks()
+    mask = None if no_row is None else rows == no_row
+    return col.take(pa.array(rows.astype(np.int64), mask=mask))
+
+
 class GPUBuildProbeJoinExecutor(Executor):
     """GPU replacement for BuildProbeJoinExecutor (sql_executors.py:325-377).
 
@@ -97,10 +146,19 @@ class GPUBuildProbeJoinExecutor(Executor):
     NULL matches nothing, as in polars, so inner and semi drop such rows
     and left and anti keep the probe's, with the key column still in its
     type and NULL (DESIGN.md §3a'''). The default refuses or mangles them
-    as before."""
+    as before.
+
+    null_payloads=True keeps NULLs in the non-key columns of both sides and
+    hands every column back in the Arrow type it arrived in: numeric
+    payloads travel as value + validity bitmap and are emitted by one
+    optional gather per column, strings by an Arrow take with the device
+    indices, and how="left" is a single left probe whose unmatched rows
+    carry NO_ROW, which the gather turns into NULL (DESIGN.md §3a''''').
+    The output of such a join is a valid input of the next one. A payload
+    type the device cannot hold raises TypeError naming the column."""
 
     def __init__(self, on=None, left_on=None, right_on=None, how="inner",
-                 key_to_keep="left", null_keys=False):
+                 key_to_keep="left", null_keys=False, null_payloads=False):
         if on is not None:
             if left_on is not None or right_on is not None:
                 raise ValueError("pass either on= or left_on=/right_on=, "
@@ -119,7 +177,12 @@ class GPUBuildProbeJoinExecutor(Executor):
         self.how = how
         self.key_to_keep = key_to_keep
         self.null_keys = bool(null_keys)
+        self.null_payloads = bool(null_payloads)
         self._build_key_masks = []  # null_keys: one bool mask per batch
+        # null_payloads: per numeric payload column, one bool mask (or None,
+        # no nulls) per build batch, and the Arrow type to hand back
+        self._build_pay_masks = {}
+        self._build_types = {}
         self.phase = "build"
         # lazy GPU state (created on first execute, never in __init__)
         self._table = None
@@ -143,27 +206,7 @@ class GPUBuildProbeJoinExecutor(Executor):
 
         if stream_id == 1:                       # build (state vstack)
             assert self.phase == "build"
-            if self._build_cols is None:
-                self._build_names = [c for c in batch.column_names]
-                self._build_cols = {c: [] for c in self._build_names}
-            for c in self._build_names:
-                col = batch.column(c)
-                if _is_stringish(col):
-                    # string columns stay Arrow until _finish_build:
-                    # KEYS go through the device string dictionary,
-                    # payloads are host-gathered at emit
-                    self._build_cols[c].append(col)
-                elif self.null_keys and c == self.right_on:
-                    # the key's mask travels beside its values, so an int
-                    # key with nulls stays int
-                    mask = np.ones(len(col), dtype=bool)
-                    if col.null_count:
-                        col, mask = staging.split_nulls(col)
-                    self._build_cols[c].append(staging.column_to_numpy(col))
-                    self._build_key_masks.append(mask)
-                else:
-                    self._build_cols[c].append(
-                        staging.column_to_numpy(col))
+            self._stage_build_batch(batch)
             return
 
         # probe
@@ -175,6 +218,35 @@ class GPUBuildProbeJoinExecutor(Executor):
             self._finish_build()
         self.phase = "probe"
         return self._probe(batch)
+
+    def _stage_build_batch(self, batch):
+        ops, shim, staging = _lazy_gpu()
+        if self._build_cols is None:
+            self._build_names = [c for c in batch.column_names]
+            self._build_cols = {c: [] for c in self._build_names}
+        for c in self._build_names:
+            col = batch.column(c)
+            if _is_stringish(col):
+                # string columns stay Arrow until _finish_build:
+                # KEYS go through the device string dictionary,
+                # payloads are host-gathered at emit
+                self._build_cols[c].append(col)
+            elif self.null_keys and c == self.right_on:
+                # the key's mask travels beside its values, so an int
+                # key with nulls stays int
+                mask = np.ones(len(col), dtype=bool)
+                if col.null_count:
+                    col, mask = staging.split_nulls(col)
+                self._build_cols[c].append(staging.column_to_numpy(col))
+                self._build_key_masks.append(mask)
+            elif self.null_payloads and c != self.right_on:
+                vals, mask = _split_payload(c, col, staging)
+                self._build_cols[c].append(vals)
+                self._build_pay_masks.setdefault(c, []).append(mask)
+                self._build_types[c] = col.type
+            else:
+                self._build_cols[c].append(
+                    staging.column_to_numpy(col))
 
     def _encode_string_keys(self, col):
         """String key column -> (i64 dictionary codes, bool mask or None).
@@ -203,6 +275,9 @@ class GPUBuildProbeJoinExecutor(Executor):
                         expected=max(1024, col.length()))
                     self._host_build[c], kmask = \
                         self._encode_string_keys(col)
+                elif self.null_payloads:
+                    # stays Arrow: taken with the build indices at emit
+                    self._build_payload_host[c] = col.combine_chunks()
                 else:
                     self._build_payload_host[c] = np.asarray(
                         col.to_pylist(), dtype=object)
@@ -246,13 +321,24 @@ class GPUBuildProbeJoinExecutor(Executor):
         for c in self._build_names:
             if c == self.right_on or c in self._build_payload_host:
                 continue
-            self._build_payload_dev[c] = shim.DevColumn.from_numpy(
-                self._host_build[c])
+            masks = self._build_pay_masks.get(c)
+            if masks is None or all(m is None for m in masks):
+                self._build_payload_dev[c] = shim.DevColumn.from_numpy(
+                    self._host_build[c])
+                continue
+            # a batch without nulls gets an all-true mask beside the others
+            mask = np.concatenate([
+                np.ones(len(v), dtype=bool) if m is None else m
+                for v, m in zip(self._build_cols[c], masks)])
+            self._build_payload_dev[c] = _payload_device(
+                ops, shim, self._host_build[c], mask)
+        self._build_pay_masks = {}
         self._build_cols = None
 
-    def _probe(self, batch):
+    def _stage_probe_keys(self, key_col):
+        """Probe key column -> (i64 host keys, bool mask or None, the
+        numeric key 0-filled under nulls or None)."""
         ops, shim, staging = _lazy_gpu()
-        key_col = batch.column(self.left_on)
         pmask = None            # null_keys: validity of the probe keys
         key_vals = None         # ... and the numeric key, 0 under nulls
         if _is_stringish(key_col):
@@ -273,6 +359,57 @@ class GPUBuildProbeJoinExecutor(Executor):
             else:
                 raise TypeError("GPU join requires integer or string keys,"
                                 " got %s" % probe_keys.dtype)
+        return probe_keys, pmask, key_vals
+
+    def _probe_null_payloads(self, batch):
+        """null_payloads=True: one probe (left = mode 3, whose misses carry
+        NO_ROW), then every column through the optional gather, which
+        writes value and validity together."""
+        import pyarrow as pa
+        ops, shim, staging = _lazy_gpu()
+        key_col = batch.column(self.left_on)
+        probe_keys, pmask, _ = self._stage_probe_keys(key_col)
+        kcol = _payload_device(ops, shim, probe_keys, pmask)
+        mode = {"inner": 0, "left": 3, "semi": 1, "anti": 2}[self.how]
+        pidx, bidx, nm = self._table.probe(kcol, mode=mode)
+        sel = bsel = None       # host copies of the indices, for strings
+        out = {}
+        for c in batch.column_names:
+            col = batch.column(c)
+            if _is_stringish(col):
+                if sel is None:
+                    sel = pidx.to_numpy(nm)
+                out[c] = _take_strings(col, sel)
+            elif c == self.left_on:
+                # the staged i64 key, with its bitmap when it has nulls
+                out[c] = _take_to_arrow(ops, kcol, pidx, nm, col.type)
+            else:
+                src = _payload_device(ops, shim,
+                                      *_split_payload(c, col, staging))
+                out[c] = _take_to_arrow(ops, src, pidx, nm, col.type)
+                src.free()
+        if bidx is not None:
+            for c, dev in self._build_payload_dev.items():
+                out[c] = _take_to_arrow(ops, dev, bidx, nm,
+                                        self._build_types[c])
+            for c, arr in self._build_payload_host.items():
+                if bsel is None:
+                    bsel = bidx.to_numpy(nm)
+                out[c] = _take_strings(arr, bsel, no_row=ops.NO_ROW)
+            bidx.free()
+        pidx.free()
+        kcol.free()
+        # as the default path's rename: the renamed key goes last
+        if self.key_to_keep == "right" and self.left_on != self.right_on:
+            out[self.right_on] = out.pop(self.left_on)
+        return pa.table(out)
+
+    def _probe(self, batch):
+        if self.null_payloads:
+            return self._probe_null_payloads(batch)
+        ops, shim, staging = _lazy_gpu()
+        key_col = batch.column(self.left_on)
+        probe_keys, pmask, key_vals = self._stage_probe_keys(key_col)
         kcol = shim.DevColumn.from_numpy(probe_keys)
         mode = {"inner": 0, "left": 0, "semi": 1, "anti": 2}[self.how]
         if pmask is None:
@@ -1075,16 +1212,24 @@ class GPUBroadcastJoinExecutor(GPUBuildProbeJoinExecutor):
     the table is built lazily from the stored host columns."""
 
     def __init__(self, small_table, on=None, small_on=None, big_on=None,
-                 suffix="_small", how="inner", null_keys=False):
+                 suffix="_small", how="inner", null_keys=False,
+                 null_payloads=False):
         if on is not None:
             assert small_on is None and big_on is None
             small_on = big_on = on
         super().__init__(left_on=big_on, right_on=small_on, how=how,
-                         null_keys=null_keys)
+                         null_keys=null_keys, null_payloads=null_payloads)
         self.suffix = suffix
         import pyarrow as pa
         if not isinstance(small_table, pa.Table):
             small_table = pa.table(small_table)
+        self._small_table = None
+        if self.null_payloads:
+            # kept as Arrow and staged like one build batch at first
+            # execute, so payload nulls and types survive
+            assert self.right_on in small_table.column_names
+            self._small_table = small_table
+            return
         self._small_host = {c: small_table.column(c).to_numpy(
             zero_copy_only=False) for c in small_table.column_names}
         assert self.right_on in self._small_host
@@ -1103,7 +1248,10 @@ class GPUBroadcastJoinExecutor(GPUBuildProbeJoinExecutor):
         batches = [b for b in batches if b is not None and len(b) > 0]
         if not batches:
             return
-        if self._table is None:
+        if self._table is None and self._small_table is not None:
+            self._stage_build_batch(self._small_table)
+            self._finish_build()
+        elif self._table is None:
             self._build_names = list(self._small_host.keys())
             self._build_cols = {c: [np.asarray(v)]
                                 for c, v in self._small_host.items()}

@@ -179,8 +179,10 @@ class JoinTable:
         self.n_build += n
 
     def probe(self, keys_col, mode=0, out_factor=1.5, n=None, valid=None):
-        """mode 0 inner / 1 semi / 2 anti. Returns (probe_idx, build_idx,
-        count) DevColumns (build_idx None for semi/anti). Grows the output
+        """mode 0 inner / 1 semi / 2 anti / 3 left. Returns (probe_idx,
+        build_idx, count) DevColumns (build_idx None for semi/anti). Left
+        is inner plus every probe row without a match once, with NO_ROW as
+        its build index. Grows the output
         and re-probes when the first guess undershoots (counted, never
         truncated). With `valid` a null probe row is a miss."""
         n = keys_col.n if n is None else n
@@ -189,7 +191,8 @@ class JoinTable:
         out_cap = max(16, int(n * out_factor))
         while True:
             probe_idx = DevColumn(np.uint32, out_cap)
-            build_idx = DevColumn(np.uint32, out_cap) if mode == 0 else None
+            build_idx = DevColumn(np.uint32, out_cap) if mode in (0, 3) \
+                else None
             cur = _count_buf()
             name, keys = ("qk_join_probe", (keys_col.ptr,)) if bitmap is None \
                 else ("qk_join_probe_valid", (keys_col.ptr, bitmap.ptr))
@@ -1323,6 +1326,38 @@ def take_nullable(col, idx, n_idx=None, stream=None):
     cnt = _count_buf()
     shim.call("qk_valid_gather", sh, c_u64(n_idx), idx.ptr, col.valid.ptr,
               valid.ptr, cnt.ptr)
+    shim.call("qk_stream_sync", sh)
+    nulls = _read_u64(cnt)
+    cnt.free()
+    return NullableColumn(values, valid, n_idx, nulls)
+
+
+NO_ROW = shim.NO_ROW    # QK_NO_ROW: JoinTable.probe(mode=3)'s "no build row"
+
+
+def take_optional(col, idx, n_idx=None, stream=None):
+    """col[idx] where idx (a device u32 index column) may hold NO_ROW:
+    such a row, and a row whose source is NULL, comes back NULL with 0 in
+    its slot. `col` is a NullableColumn or a plain DevColumn (every row
+    valid). One qk_take_opt_* launch writes values, bitmap and null count;
+    every index other than NO_ROW must be below col.n. Returns a
+    NullableColumn."""
+    n_idx = idx.n if n_idx is None else int(n_idx)
+    sh = stream.handle if stream else None
+    src = col.values if isinstance(col, NullableColumn) else col
+    fn = shim._DTYPE_TAKE_OPT.get(src.dtype)
+    if fn is None:
+        raise TypeError("take_optional: unsupported dtype %s" % src.dtype)
+    values = DevColumn(src.dtype, n_idx)
+    nb = valid_nbytes(n_idx)
+    valid = DevBuffer(nb)
+    # the kernel writes whole words up to ceil(n_idx / 64); the slack word
+    # behind them is zeroed here
+    shim.call("qk_dmemset", c_vp(valid.ptr.value + nb - 8), 0, c_u64(8))
+    cnt = _count_buf()
+    shim.call(fn, sh, c_u64(n_idx), idx.ptr, src.ptr,
+              col.valid.ptr if isinstance(col, NullableColumn) else None,
+              values.ptr, valid.ptr, cnt.ptr)
     shim.call("qk_stream_sync", sh)
     nulls = _read_u64(cnt)
     cnt.free()

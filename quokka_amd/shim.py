@@ -138,6 +138,10 @@ _SIGS = {
     "qk_valid_expand": [c_vp, c_u64, c_vp, c_vp, c_vp, c_u32],
     "qk_valid_to_u8": [c_vp, c_u64, c_vp, c_vp],
     "qk_valid_gather": [c_vp, c_u64, c_vp, c_vp, c_vp, c_vp],
+    "qk_take_opt_i64": [c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "qk_take_opt_f64": [c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "qk_take_opt_i32": [c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "qk_take_opt_u8": [c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "qk_pq_walk_pages": [c_vp, c_u64, c_u64, c_i64, c_vp, c_i64, c_vp],
     "qk_snappy_pages": [c_vp, c_u64, c_vp, c_vp, c_vp, c_vp],
     "qk_gzip_pages": [c_vp, c_u64, c_vp, c_vp, c_vp, c_vp],
@@ -215,6 +219,7 @@ def device_count():
 
 
 JOIN_EMPTY = np.int64(-(2 ** 63))  # QK_JOIN_EMPTY
+NO_ROW = 0xFFFFFFFF                # QK_NO_ROW: build index of "no build row"
 
 # launch shape of the generic operators: up to BLOCK_THREADS * MAX_BLOCKS
 # rows the sort and the partition scatter give each block one tile, above
@@ -362,6 +367,13 @@ _DTYPE_GATHER = {
     np.dtype(np.int32): "qk_gather_i32",
     np.dtype(np.uint8): "qk_gather_u8",
     np.dtype(np.uint32): "qk_gather_i32",  # same width
+}
+_DTYPE_TAKE_OPT = {
+    np.dtype(np.int64): "qk_take_opt_i64",
+    np.dtype(np.float64): "qk_take_opt_f64",
+    np.dtype(np.int32): "qk_take_opt_i32",
+    np.dtype(np.uint8): "qk_take_opt_u8",
+    np.dtype(np.uint32): "qk_take_opt_i32",  # same width
 }
 
 
