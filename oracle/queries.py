@@ -217,7 +217,8 @@ def q10(li, orders, customer, nation, limit=20):
     rev = li["l_extendedprice"][lmask] * (1.0 - li["l_discount"][lmask])
     ncust = int(customer["c_custkey"].max()) + 2
     rev_by_cust = np.bincount(cust, weights=rev, minlength=ncust)
-    ck = np.nonzero(rev_by_cust > 0)[0]
+    # a customer is a group because a line reached it, whatever its sum
+    ck = np.nonzero(np.bincount(cust, minlength=ncust))[0]
     row = ck - 1                                  # custkey is dense 1..N
     out = {
         "c_custkey": ck.astype(np.int64),
@@ -393,9 +394,13 @@ def q15(li, supplier):
                       weights=(li["l_extendedprice"][m]
                                * (1.0 - li["l_discount"][m])),
                       minlength=nkey)
-    mx = rev.max()
-    winners = np.nonzero(rev == mx)[0]
-    return winners.astype(np.int64), float(mx)
+    # only suppliers a line reached are rows of the revenue view: an empty
+    # window has no winners (max over no rows is NULL; reported as 0.0)
+    seen = np.nonzero(np.bincount(li["l_suppkey"][m], minlength=nkey))[0]
+    if not len(seen):
+        return seen.astype(np.int64), 0.0
+    mx = rev[seen].max()
+    return seen[rev[seen] == mx].astype(np.int64), float(mx)
 
 
 # Q19 branch constants (tpch_ref.py:582-620), resolved to dictionary
@@ -512,7 +517,9 @@ def q20(li, part, partsupp, supplier, nation):
     pm = forest[partsupp["ps_partkey"]]
     pskey = partsupp["ps_partkey"][pm] * S + partsupp["ps_suppkey"][pm]
     pos = np.searchsorted(kk, pskey)
-    have = (pos < len(kk)) & (kk[np.minimum(pos, len(kk) - 1)] == pskey)
+    have = np.zeros(len(pskey), dtype=bool)
+    if len(kk):
+        have = (pos < len(kk)) & (kk[np.minimum(pos, len(kk) - 1)] == pskey)
     thr = np.zeros(len(pskey))
     thr[have] = 0.5 * qty[pos[have]]
     # SQL: availqty > (scalar subquery); an EMPTY subquery yields NULL
@@ -559,9 +566,9 @@ def q9(li, orders, supplier, part, partsupp, nation):
     out = {}
     for nk in range(25):
         for y in np.unique(yr):
-            v = amount[(sn == nk) & (yr == y)].sum()
-            if v != 0.0:
-                out[(names[nk], int(y))] = float(v)
+            sel = (sn == nk) & (yr == y)
+            if sel.any():           # a group exists once a row reached it
+                out[(names[nk], int(y))] = float(amount[sel].sum())
     return out
 
 
