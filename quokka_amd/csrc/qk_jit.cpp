@@ -268,19 +268,44 @@ static std::string gen_agg_source(const char *pred, const char *group_expr,
                                   const int *coltypes) {
   auto op = [&](int a) { return agg_ops ? agg_ops[a] : 0; };
   auto init_of = [&](int a) {
-    return op(a) == 1 ? "(1.0/0.0)" : op(a) == 2 ? "(-1.0/0.0)" : "0.0";
+    return op(a) ? "QK_MM_SKIP" : "0.0";
   };
   std::string s;
   s += "#define BLOCK 256\n#define WAVE 64\n";
   s += "typedef unsigned long long u64; typedef unsigned u32;\n";
-  s += "__device__ inline void qk_atomic_mm(double* a, double v, int mx) {\n"
-       "  unsigned long long* p = (unsigned long long*)a;\n"
-       "  unsigned long long old = *p;\n"
+  // MIN/MAX state, in registers and in `out` alike (the slot rules of
+  // atomic_mm_f64 in quokka_amd.hip): QK_MM_NONE = nothing met yet, the
+  // canonical NaN = only NaN met, else the extreme of the numbers met.
+  // qk_mm folds two states; an input row is a state too once it has gone
+  // through qk_num (any NaN -> the canonical one), which the accumulate
+  // below applies to every MIN/MAX expression but one that spells a NULL
+  // as QK_MM_SKIP itself (jit.py, nullable columns).
+  s += "#define QK_MM_NONE 0x7FF8C0DE0000A66FULL\n"
+       "#define QK_MM_NAN 0x7FF8000000000000ULL\n"
+       "#define QK_MM_SKIP __longlong_as_double((long long)QK_MM_NONE)\n"
+       "__device__ inline u64 qk_bits(double v) {\n"
+       "  return (u64)__double_as_longlong(v); }\n"
+       "__device__ inline double qk_mm(double a, double b, int mx) {\n"
+       "  if (b != b) {\n"
+       "    if (a == a || qk_bits(b) == QK_MM_NONE) return a;\n"
+       "    return __longlong_as_double((long long)QK_MM_NAN);\n"
+       "  }\n"
+       "  if (a != a) return b;\n"
+       "  return mx ? (a < b ? b : a) : (b < a ? b : a);\n"
+       "}\n"
+       "__device__ inline double qk_num(double v) {\n"
+       "  return v == v ? v : __longlong_as_double((long long)QK_MM_NAN);\n"
+       "}\n"
+       "__device__ inline void qk_atomic_mm(double* a, double v, int mx) {\n"
+       "  u64* p = (u64*)a;\n"
+       "  u64 old = *p;\n"
+       "  bool vnan = v != v;\n"
        "  for (;;) {\n"
-       "    double cur = __longlong_as_double(old);\n"
-       "    if (mx ? (v <= cur) : (v >= cur)) return;\n"
-       "    unsigned long long prev = atomicCAS(p, old,"
-       " __double_as_longlong(v));\n"
+       "    double cur = __longlong_as_double((long long)old);\n"
+       "    bool take = vnan ? old == QK_MM_NONE\n"
+       "                     : (mx ? !(cur >= v) : !(cur <= v));\n"
+       "    if (!take) return;\n"
+       "    u64 prev = atomicCAS(p, old, qk_bits(v));\n"
        "    if (prev == old) return;\n"
        "    old = prev;\n  }\n}\n";
   s += "extern \"C\" __global__ __launch_bounds__(BLOCK) void jit_agg(\n";
@@ -339,10 +364,18 @@ static std::string gen_agg_source(const char *pred, const char *group_expr,
         std::string acc = "acc_" + std::to_string(g) + "_" +
                           std::to_string(a);
         std::string val = "(double)(" + ren(agg_exprs[a]) + ")";
+        // a MIN/MAX input: any NaN -> the canonical one, so that no column
+        // value can be taken for QK_MM_SKIP. An expression that names
+        // QK_MM_SKIP itself (jit.py's NULL branch) has done so on its
+        // value branch and is taken as it is.
+        if (op(a) && !strstr(agg_exprs[a], "QK_MM_SKIP"))
+          val = "qk_num(" + val + ")";
         if (op(a) == 1)
-          b += pfx + "    " + acc + " = fmin(" + acc + ", " + val + ");\n";
+          b += pfx + "    " + acc + " = qk_mm(" + acc + ", " + val +
+               ", 0);\n";
         else if (op(a) == 2)
-          b += pfx + "    " + acc + " = fmax(" + acc + ", " + val + ");\n";
+          b += pfx + "    " + acc + " = qk_mm(" + acc + ", " + val +
+               ", 1);\n";
         else
           b += pfx + "    " + acc + " += " + val + ";\n";
       }
@@ -404,8 +437,8 @@ static std::string gen_agg_source(const char *pred, const char *group_expr,
   for (int g = 0; g < ngroups; g++)
     for (int a = 0; a < naggs; a++) {
       std::string acc = "acc_" + std::to_string(g) + "_" + std::to_string(a);
-      const char *comb = op(a) == 1 ? "t = fmin(t, __shfl_down(t, off))"
-                         : op(a) == 2 ? "t = fmax(t, __shfl_down(t, off))"
+      const char *comb = op(a) == 1 ? "t = qk_mm(t, __shfl_down(t, off), 0)"
+                         : op(a) == 2 ? "t = qk_mm(t, __shfl_down(t, off), 1)"
                                       : "t += __shfl_down(t, off)";
       s += "  { double t = " + acc + ";\n"
            "    for (int off = WAVE / 2; off > 0; off >>= 1)\n"
@@ -424,18 +457,13 @@ static std::string gen_agg_source(const char *pred, const char *group_expr,
                "    for (int w = 0; w < BLOCK / WAVE; w++) t += lds[w][" +
                idx + "];\n"
                "    if (t != 0.0) atomicAdd(&out[" + idx + "], t);\n";
-      else if (op(a) == 1)
-        body = "    double t = (1.0/0.0);\n"
-               "    for (int w = 0; w < BLOCK / WAVE; w++)"
-               " t = fmin(t, lds[w][" + idx + "]);\n"
-               "    if (t < (1.0/0.0)) qk_atomic_mm(&out[" + idx +
-               "], t, 0);\n";
       else
-        body = "    double t = (-1.0/0.0);\n"
+        body = "    double t = QK_MM_SKIP;\n"
                "    for (int w = 0; w < BLOCK / WAVE; w++)"
-               " t = fmax(t, lds[w][" + idx + "]);\n"
-               "    if (t > (-1.0/0.0)) qk_atomic_mm(&out[" + idx +
-               "], t, 1);\n";
+               " t = qk_mm(t, lds[w][" + idx + "], " +
+               std::to_string(op(a) - 1) + ");\n"
+               "    if (qk_bits(t) != QK_MM_NONE) qk_atomic_mm(&out[" + idx +
+               "], t, " + std::to_string(op(a) - 1) + ");\n";
       s += "  if (threadIdx.x == " + std::to_string(g * naggs + a) +
            " % BLOCK && threadIdx.x < BLOCK) {\n" + body + "  }\n";
     }

@@ -1952,29 +1952,43 @@ extern "C" int qk_gen_supplier(void *stream, uint64_t n, uint64_t row_offset,
 }
 
 // ---- group-by i64 -> f64 sums ----------------------------------------
-// f64 atomic min/max via CAS on the bit pattern (ordered-compare loop)
-__device__ inline void atomic_min_f64(double *addr, double v) {
+// f64 atomic min/max via CAS on the bit pattern. A MIN/MAX slot holds one
+// of three things: QK_MM_NONE (no input yet; the host reads it back as
+// +inf / -inf), the canonical quiet NaN (every input so far was NaN), or
+// the running extreme of the non-NaN inputs. A number replaces either NaN
+// pattern and then competes by ordered compare; a NaN input is written as
+// the canonical NaN, and only over QK_MM_NONE, so an input whose payload
+// happens to equal QK_MM_NONE never reaches a slot. MIN/MAX therefore skip
+// NaN beside numbers and an all-NaN group is NaN (float edge
+// values in aggregates).
+#define QK_MM_NONE 0x7FF8C0DE0000A66FULL  // ops.MM_NONE_BITS, qk_jit.cpp
+#define QK_MM_NAN 0x7FF8000000000000ULL
+template <bool IS_MAX>
+__device__ inline void atomic_mm_f64(double *addr, double v) {
   unsigned long long *a = (unsigned long long *)addr;
   unsigned long long cur = *a;
-  while (__longlong_as_double((long long)cur) > v) {
-    unsigned long long prev =
-        atomicCAS(a, cur, (unsigned long long)__double_as_longlong(v));
+  bool vnan = v != v;
+  unsigned long long vb =
+      vnan ? QK_MM_NAN : (unsigned long long)__double_as_longlong(v);
+  for (;;) {
+    double c = __longlong_as_double((long long)cur);
+    // !(c >= v) holds for c < v and for a slot with either NaN pattern
+    bool take = vnan ? cur == QK_MM_NONE
+                     : (IS_MAX ? !(c >= v) : !(c <= v));
+    if (!take) break;
+    unsigned long long prev = atomicCAS(a, cur, vb);
     if (prev == cur) break;
     cur = prev;
   }
+}
+__device__ inline void atomic_min_f64(double *addr, double v) {
+  atomic_mm_f64<false>(addr, v);
 }
 __device__ inline void atomic_max_f64(double *addr, double v) {
-  unsigned long long *a = (unsigned long long *)addr;
-  unsigned long long cur = *a;
-  while (__longlong_as_double((long long)cur) < v) {
-    unsigned long long prev =
-        atomicCAS(a, cur, (unsigned long long)__double_as_longlong(v));
-    if (prev == cur) break;
-    cur = prev;
-  }
+  atomic_mm_f64<true>(addr, v);
 }
 
-// agg_ops[c]: 0 = SUM (slot init 0), 1 = MIN (init +inf), 2 = MAX (-inf)
+// agg_ops[c]: 0 = SUM (slot init 0), 1 = MIN, 2 = MAX (both QK_MM_NONE)
 __global__ void __launch_bounds__(BLOCK) k_groupby_sum(
     uint64_t n, const int64_t *__restrict__ keys, const double *const *vals,
     const int32_t *__restrict__ agg_ops, int nvals, int rstride,
@@ -3389,7 +3403,8 @@ extern "C" int qk_nullword_to_valid(void *stream, uint64_t g,
 // ---- dense accumulate over key-dictionary codes ------------------------
 // acc: one record of rstride (pow2 >= nvals) doubles per code, so a row
 // touches one line (the interleaved records of k_groupby_sum without the
-// key word). Records [first, first + count) start at the op identities.
+// key word). Records [first, first + count) start at `inits` (ops.py: 0
+// for SUM, QK_MM_NONE for MIN/MAX).
 __global__ void __launch_bounds__(BLOCK) k_groupby_dense_init(
     uint64_t first, uint64_t count, int rstride, int nvals,
     const double *__restrict__ inits, double *__restrict__ acc) {

@@ -776,7 +776,10 @@ class GPUAggExecutor(Executor):
     refuses. By default a NULL in a value column arrives as NaN
     (an integer column with nulls turns float on the way) and is
     accumulated like any other value: one NULL makes its group's SUM NaN,
-    and a MIN / MAX keeps whatever the comparison with NaN leaves."""
+    and a MIN / MAX skips it like any NaN. NaN values follow Acero on every
+    path: SUM with a NaN is NaN, MIN / MAX skip NaN beside other values,
+    and a MIN / MAX whose inputs were all NaN is NaN, not the identity and,
+    with null_values=True, not NULL (DESIGN.md §3a'''''')."""
 
     def __init__(self, groupby_keys, orderby_keys, sql_statement,
                  device_keys=False, null_keys=False, null_values=False):
@@ -1625,13 +1628,13 @@ class GPUTopKExecutor(Executor):
         cols = []
         for key, desc in zip(reversed(self.sort_keys),
                              reversed(self.descending)):
-            v = np.asarray(self.state.column(key).to_numpy(
-                zero_copy_only=False))
+            col = self.state.column(key)
+            v = np.asarray(col.to_numpy(zero_copy_only=False))
             if desc:
                 # descending = ascending on the reversed rank of the
                 # distinct values: no arithmetic on the key itself, so
                 # strings, unsigned and INT64_MIN keys order like any
-                # other. NaN (a null) stays last, as it is ascending.
+                # other. NaN stays last, as it is ascending.
                 _, inv = np.unique(v, return_inverse=True)
                 inv = inv.reshape(-1)
                 rank = inv.max() - inv
@@ -1639,6 +1642,11 @@ class GPUTopKExecutor(Executor):
                     rank[np.isnan(v)] = len(v)
                 v = rank
             cols.append(v)
+            if col.null_count and v.dtype.kind in "fiu":
+                # a float NULL arrives as NaN: it sorts after the NaN
+                # values in both directions (Acero's nulls-at-end order)
+                cols.append(np.asarray(col.is_null().to_numpy(
+                    zero_copy_only=False)))
         order = np.lexsort(cols)[: self.k]
         return self.state.take(order)
 

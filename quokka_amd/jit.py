@@ -754,7 +754,11 @@ class JitAggregate:
     counts the rows where it is not; COUNT(*) counts rows. A group whose
     inputs were ALL null reads back as the aggregate's identity (0 /
     +inf / -inf), not as NULL: put COUNT(col) beside it to tell the two
-    apart. Group keys must be non-null; a nullable one raises TypeError."""
+    apart. Group keys must be non-null; a nullable one raises TypeError.
+
+    NaN inputs (DESIGN.md §3a''''''): SUM with a NaN is NaN; MIN/MAX skip
+    NaN beside other values, and a group whose MIN/MAX inputs were all NaN
+    reads back as NaN, not as the identity."""
 
     def __init__(self, schema, group_keys, aggs, predicate=None,
                  string_dicts=None, nullable=()):
@@ -806,11 +810,16 @@ class JitAggregate:
                 e, _ = translate_arith(inner, schema, tr)
                 self.agg_ops.append({"sum": 0, "min": 1, "max": 2}[fn])
             v = tr._valid_expr(tr._touched)
-            if v:
+            if v and self.agg_ops[-1]:
+                # a NULL input leaves a MIN/MAX accumulator alone: it is
+                # spelt as the no-input pattern, which no value can be
+                # taken for once qk_num has made every NaN the canonical
+                # one (csrc gen_agg_source does that for expressions that
+                # do not name QK_MM_SKIP)
+                e = "((%s) ? qk_num((double)(%s)) : QK_MM_SKIP)" % (v, e)
+            elif v:
                 # a NULL input leaves the accumulator alone
-                e = "((%s) ? (double)(%s) : %s)" % (
-                    v, e, ("0.0", "(1.0/0.0)", "(-1.0/0.0)")[
-                        self.agg_ops[-1]])
+                e = "((%s) ? (double)(%s) : 0.0)" % (v, e)
             agg_exprs.append(e)
             self.agg_names.append(alias or a.strip())
         self.naggs = len(agg_exprs)
@@ -841,16 +850,16 @@ class JitAggregate:
         self.prog = prog
 
     def make_acc(self):
-        """Accumulator initialized to each aggregate's identity
-        (0 / +inf / -inf) — MIN/MAX groups never touched keep it."""
+        """Accumulator initialized to 0 for SUM/COUNT and to the no-input
+        pattern of MIN/MAX slots (ops.MM_NONE_BITS), which read() gives
+        back as the identity +inf / -inf."""
         from .shim import DevBuffer, c_vp as _vp
+        from .ops import MM_NONE_BITS
         b = DevBuffer(self.ngroups * self.naggs * 8)
-        init = np.zeros((self.ngroups, self.naggs), dtype=np.float64)
+        init = np.zeros((self.ngroups, self.naggs), dtype=np.uint64)
         for a, o in enumerate(self.agg_ops):
-            if o == 1:
-                init[:, a] = np.inf
-            elif o == 2:
-                init[:, a] = -np.inf
+            if o:
+                init[:, a] = MM_NONE_BITS
         flat = np.ascontiguousarray(init.reshape(-1))
         shim.call("qk_h2d", b.ptr, flat.ctypes.data_as(_vp),
                   c_u64(flat.nbytes))
@@ -879,11 +888,18 @@ class JitAggregate:
                                % lib.qk_jit_last_error().decode())
 
     def read(self, acc):
-        """d2h -> (ngroups, naggs) f64."""
+        """d2h -> (ngroups, naggs) f64. A MIN/MAX that met no value reads
+        as +inf / -inf; one that met only NaN reads as NaN."""
+        from .ops import MM_NONE_BITS
         host = np.zeros(self.ngroups * self.naggs, dtype=np.float64)
         shim.call("qk_d2h", host.ctypes.data_as(c_vp), acc.ptr,
                   c_u64(host.nbytes))
-        return host.reshape(self.ngroups, self.naggs)
+        out = host.reshape(self.ngroups, self.naggs)
+        for a, o in enumerate(self.agg_ops):
+            if o:
+                none = out[:, a].view(np.uint64) == MM_NONE_BITS
+                out[none, a] = np.inf if o == 1 else -np.inf
+        return out
 
     def free(self):
         if self.prog:

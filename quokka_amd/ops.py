@@ -97,6 +97,14 @@ def check_no_sentinel_key(keys, operator, column):
             "not supported" % (operator, column, int(shim.JOIN_EMPTY)))
 
 
+# A MIN/MAX slot that no input has reached holds this quiet-NaN pattern
+# (QK_MM_NONE in csrc): a NaN input turns it into the canonical NaN, a
+# number replaces either, and the read-out maps what is left of it to the
+# op's identity. So MIN/MAX skip NaN beside numbers, an all-NaN group is
+# NaN, and an untouched slot still reads +inf / -inf.
+MM_NONE_BITS = 0x7FF8C0DE0000A66F
+
+
 def _pow2_at_least(n):
     c = 1
     while c < n:
@@ -232,7 +240,16 @@ class GroupByI64:
     marker). update() takes device keys and does not look at them;
     callers with host keys use check_no_sentinel_key first."""
 
-    AGG_INIT = {0: 0.0, 1: float("inf"), 2: float("-inf")}  # SUM/MIN/MAX
+    # what an aggregate without input READS as (SUM/MIN/MAX); a MIN/MAX
+    # slot itself starts at MM_NONE_BITS, see _slot_inits
+    AGG_INIT = {0: 0.0, 1: float("inf"), 2: float("-inf")}
+
+    @classmethod
+    def _slot_inits(cls, agg_ops):
+        """What a fresh record holds: 0 for SUM, MM_NONE_BITS for MIN/MAX
+        (read back as AGG_INIT; see atomic_mm_f64 for why not +-inf)."""
+        bits = [MM_NONE_BITS if op else 0 for op in agg_ops] or [0]
+        return np.asarray(bits, dtype=np.uint64).view(np.float64)
 
     def __init__(self, expected_groups, nvals, stream=None, agg_ops=None):
         """agg_ops: per value column 0=SUM, 1=MIN, 2=MAX (default all SUM),
@@ -252,8 +269,7 @@ class GroupByI64:
             self.rstride <<= 1
         self.table = DevColumn(np.int64, self.cap * self.rstride)
         self._inits_dev = DevColumn.from_numpy(
-            np.asarray([self.AGG_INIT[op] for op in self.agg_ops],
-                       dtype=np.float64))
+            self._slot_inits(self.agg_ops))
         sh = stream.handle if stream else None
         shim.call("qk_groupby_init", sh, self.table.ptr, c_u64(self.cap),
                   self.rstride, self.nvals, self._inits_dev.ptr)
@@ -297,8 +313,10 @@ class GroupByI64:
     def _grow(self, need_groups):
         """Rebuild into a larger table (>= 4x the needed group count):
         extract the accumulated (keys, sums) and re-insert them — correct
-        for SUM (adds into the zero identity) and MIN/MAX (single value vs
-        the op identity) alike. Mirrors GPUDistinctExecutor._grow."""
+        for SUM (adds into the zero start) and MIN/MAX alike: the fresh
+        slot holds MM_NONE_BITS, which a number replaces and over which
+        the NaN of an all-NaN group is written back as the canonical NaN.
+        Mirrors GPUDistinctExecutor._grow."""
         keys, sums = self.extract()
         old_groups = len(keys)
         self.table.free()
@@ -921,8 +939,7 @@ class DenseAcc:
         self.stream = stream
         self.rstride = _pow2_at_least(max(1, self.nvals))
         self._inits_dev = DevColumn.from_numpy(
-            np.asarray([self.AGG_INIT[op] for op in self.agg_ops] or [0.0],
-                       dtype=np.float64))
+            GroupByI64._slot_inits(self.agg_ops))
         self._ops_dev = None
         if any(self.agg_ops):
             self._ops_dev = DevColumn.from_numpy(
@@ -944,8 +961,10 @@ class DenseAcc:
                   self._inits_dev.ptr)
 
     def _grow_acc(self, need):
-        """Records of existing codes move by device copy; the new capacity
-        starts at the op identities, and its seen words at 0."""
+        """Records of existing codes move by device copy, bit for bit (a
+        MIN/MAX slot's no-input and all-NaN patterns included); the new
+        capacity starts at the slot starts of _slot_inits (0 for SUM,
+        MM_NONE_BITS for MIN/MAX), and its seen words at 0."""
         new_cap = _pow2_at_least(2 * need)
         new = DevColumn(np.float64, new_cap * self.rstride)
         sh = self.stream.handle if self.stream else None
@@ -1039,14 +1058,20 @@ class DenseAcc:
 
     def extract(self, g):
         """-> np.float64 [nvals, g], column i the record of code i. An
-        aggregate that met no value holds its op identity."""
+        aggregate that met no value reads as its op identity (AGG_INIT;
+        the MM_NONE_BITS of such a MIN/MAX slot is mapped here)."""
         recs = np.empty(g * self.rstride, dtype=np.float64)
         if g and self.nvals:
             shim.call("qk_stream_sync",
                       self.stream.handle if self.stream else None)
             shim._bounce.d2h(recs, self.acc.ptr)
-        return np.ascontiguousarray(
+        out = np.ascontiguousarray(
             recs.reshape(g, self.rstride)[:, :self.nvals].T)
+        for c, op in enumerate(self.agg_ops):
+            if op:  # a MIN/MAX slot no value reached
+                out[c][out[c].view(np.uint64) == MM_NONE_BITS] = \
+                    self.AGG_INIT[op]
+        return out
 
     def extract_valid(self, g):
         """-> bool [nvals, g], False where that aggregate of code i is
